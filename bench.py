@@ -19,9 +19,16 @@ world*B queries x corpus/world rows = B x corpus = constant, and per-GPU
 embed work is B docs = constant, so this is weak scaling (per-GPU work
 fixed; QPS should scale ~linearly with N).
 
-Recall is measured (untimed) against full-precision fp32 exact search over
-the full corpus for a sample of queries; brute-force scoring makes >=0.95
-structural, the check guards the bf16 kernels.
+A plain run sets up, warms up, times --steps steps and prints one JSON
+result line. --dump-outputs DIR also writes what the last timed step
+returned (query embeddings, top-k scores and row ids) as DIR/<name>.npy;
+the seeds are fixed, so equal arguments give equal inputs run after run.
+
+With --full, recall is measured (untimed, after the timed steps) against
+full-precision fp32 exact search over the full corpus for a sample of
+queries, and the embed/search phase split is printed; brute-force scoring
+makes >=0.95 structural, the check guards the bf16 kernels. Without --full
+the result line reports recall_at_k_vs_fp32_exact as null.
 
 Data is synthetic (no network in the environment); encoder weights are
 random-init at the exact bge-m3 / XLM-R-large shape.
@@ -40,6 +47,30 @@ import torch.distributed as dist
 def log(rank, *a):
     if rank == 0:
         print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # all --dump-outputs files together
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy. Floating tensors are
+    stored as float32 (float64 stays float64), integer ones as float64
+    (row ids < 2^53 are exact). An array over its share of the budget is
+    replaced by a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        itemsize = 8 if wide else 4
+        if t.numel() * itemsize > share:
+            pick = np.sort(np.random.default_rng(0x6E6F726E).integers(
+                0, t.numel(), size=share // itemsize))
+            t = t.reshape(-1)[torch.from_numpy(pick).to(t.device)]
+        a = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def setup_dist(args):
@@ -217,6 +248,8 @@ def graph_bench(args, rank, world, local_rank):
     # sanity: ranks sum to ~1
     total = float(r.sum()) if world == 1 else float(r.sum())
     iters_per_s = args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pagerank": r})
     if rank == 0:
         out = {
             "metric": "PageRank iterations/s on 1B-edge synthetic CSR (GPU-sharded, halo exchange)",
@@ -256,12 +289,22 @@ def main():
     p.add_argument("--seq-len", type=int, default=256)
     p.add_argument("--k", type=int, default=10)
     p.add_argument("--layers", type=int, default=24)
-    p.add_argument("--skip-recall", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the untimed extras: "
+                        "the recall check against fp32 exact search and the "
+                        "embed/search phase breakdown (a plain run only "
+                        "sets up, warms up, times --steps steps and prints)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as "
+                        "DIR/<name>.npy (float32/float64)")
+    p.add_argument("--skip-recall", action="store_true",
+                   help="with --full: leave out the recall check")
     p.add_argument("--quant", choices=["none", "int8"], default="none",
                    help="int8: 1 B/elem corpus scored by the i8 MFMA "
                         "kernel (2x capacity; NOT the headline config — "
                         "dtype is reported as int8)")
-    p.add_argument("--timing", action="store_true", help="print phase breakdown")
+    p.add_argument("--timing", action="store_true",
+                   help="print phase breakdown (implied by --full)")
     p.add_argument("--no-pipeline", action="store_true",
                    help="disable embed/search stream overlap (sequential steps)")
     p.add_argument("--recall-queries", type=int, default=8)
@@ -387,11 +430,56 @@ def main():
     for _ in range(args.warmup):
         last_q, _, _ = one_step()
     if pipelined:
+        if last_q is None:  # --warmup 0: the pipeline still needs a batch
+            last_q = gather_queries(embed_batch())
         last_q, _ = pipe_step(last_q)  # warm both streams
     if device.type == "cuda":
         torch.cuda.synchronize()
 
-    if args.timing and device.type == "cuda":
+    # --- timed region ---
+    if world > 1:
+        dist.barrier()
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    t_start = time.time()
+    last_out = None  # what the last timed step returned (--dump-outputs)
+    if pipelined:
+        for _ in range(args.steps):
+            searched_q = last_q
+            last_q, (top_s, top_i) = pipe_step(last_q)
+            last_out = (last_q, searched_q, top_s, top_i)
+    else:
+        for _ in range(args.steps):
+            qg, top_s, top_i = one_step()
+            last_out = (qg, qg, top_s, top_i)
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    elapsed = time.time() - t_start
+
+    # max over ranks
+    if world > 1:
+        t = torch.tensor([elapsed], device=device if device.type == "cuda" else None)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0 and last_out is not None:
+        new_q, searched_q, top_s, top_i = last_out
+        dump_outputs(args.dump_outputs, {
+            # embeddings of the last step's fresh batch
+            "query_embeddings": new_q,
+            # the batch the last step searched (pipelined: the one before)
+            # and its top-k over the corpus
+            "searched_embeddings": searched_q,
+            "topk_scores": top_s,
+            "topk_indices": top_i,
+        })
+
+    # --- untimed extras (--full): phase breakdown + recall check. They run
+    # after the timed steps so that these see the same random stream (hence
+    # the same inputs) with and without --full. ---
+    if (args.full or args.timing) and device.type == "cuda":
         def _t(fn, iters=5):
             torch.cuda.synchronize()
             t0 = time.time()
@@ -412,10 +500,9 @@ def main():
                   f"search {ms_search:.1f} ms/batch ({args.batch/ms_search*1000:.0f} qps; "
                   f"{shard_rows*args.dim*2/ms_search/1e9:.2f} TB/s shard read)")
 
-    # --- recall check (untimed): production path vs fp32 exact over full corpus ---
+    # recall check (untimed): production path vs fp32 exact over full corpus
     recall = None
-    if not args.skip_recall:
-        from nornicdb_amd.ops import knn_search
+    if args.full and not args.skip_recall:
         nq = args.recall_queries
         tokens = torch.randint(0, vocab, (nq, args.seq_len), device=device,
                                generator=torch.Generator(device=device).manual_seed(99))
@@ -444,30 +531,6 @@ def main():
             hit += len(set(pi[r].tolist()) & set(ei[r].tolist()))
         recall = hit / (nq * args.k)
         log(rank, f"[bench] recall@{args.k} vs fp32 exact (full corpus): {recall:.4f}")
-
-    # --- timed region ---
-    if world > 1:
-        dist.barrier()
-    if device.type == "cuda":
-        torch.cuda.synchronize()
-    t_start = time.time()
-    if pipelined:
-        for _ in range(args.steps):
-            last_q, _ = pipe_step(last_q)
-    else:
-        for _ in range(args.steps):
-            one_step()
-    if device.type == "cuda":
-        torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.time() - t_start
-
-    # max over ranks
-    if world > 1:
-        t = torch.tensor([elapsed], device=device if device.type == "cuda" else None)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
 
     total_queries = args.steps * args.batch * world
     qps = total_queries / elapsed

@@ -328,7 +328,9 @@ def test_explicit_tx_rollback_undoes_writes():
     from nornicdb_amd.embed import MockEmbedder
 
     mgr = open_db(embedder=MockEmbedder(8), dims=8)
-    srv = BoltServer(lambda db: mgr.get(db).executor,
+    # port=0: an ephemeral port, so a listener that an earlier test's
+    # uncollected event loop still holds on 7687 cannot make the bind fail
+    srv = BoltServer(lambda db: mgr.get(db).executor, port=0,
                      tx_factory=lambda name: mgr.get(name).begin_tx())
 
     async def run():
@@ -390,7 +392,7 @@ def test_explicit_tx_rollback_undoes_writes():
         await send(0x0F)   # RESET
         await recv()
         w.close()
-        await srv._server.wait_closed() if False else None
+        srv.close()
 
     asyncio.new_event_loop().run_until_complete(run())
     rows = mgr.get().cypher("MATCH (n:TxB) RETURN n.x ORDER BY n.x").rows
@@ -410,7 +412,7 @@ def test_point_values_over_bolt():
     from nornicdb_amd.embed import MockEmbedder
 
     mgr = open_db(embedder=MockEmbedder(8), dims=8)
-    srv = BoltServer(lambda db: mgr.get(db).executor)
+    srv = BoltServer(lambda db: mgr.get(db).executor, port=0)
 
     async def run():
         await srv.start()
@@ -454,5 +456,6 @@ def test_point_values_over_bolt():
         assert g.fields[0] == 4979 and g.fields[1] == 9.0
         await recv()   # summary
         w.close()
+        srv.close()
 
     asyncio.new_event_loop().run_until_complete(run())

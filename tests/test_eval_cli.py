@@ -49,7 +49,8 @@ class TestCLI:
         # one subprocess for all three commands: each interpreter start
         # pays the torch import (~10 s), so chaining keeps the suite fast
         import os
-        env = {**os.environ, "PYTHONPATH": "."}
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        env = {**os.environ, "PYTHONPATH": repo}
         d = str(tmp_path / "data")
         f = tmp_path / "imp.json"
         f.write_text(json.dumps({

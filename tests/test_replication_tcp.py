@@ -174,6 +174,13 @@ tr = TcpTransport("standby", {{k: tuple(v) for k, v in peers.items()}})
 applied = []
 s = HAStandby("standby", "primary", tr, apply_fn=applied.append)
 s.PROMOTE_AFTER = 0.6
+print("READY", flush=True)   # listening + handler registered
+# the failover watch starts once the primary has been heard: the parent
+# starts the primary only now, and its imports alone take longer than
+# PROMOTE_AFTER
+deadline = time.time() + 60
+while not applied and time.time() < deadline:
+    time.sleep(0.02)
 deadline = time.time() + 15
 while time.time() < deadline:
     time.sleep(0.05)
@@ -193,7 +200,10 @@ def test_ha_two_process_failover(tmp_path):
         [sys.executable, "-c", _HA_STANDBY.format(repo=REPO),
          json.dumps(peers), out],
         stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    time.sleep(0.3)
+    # entries sent before the standby listens are lost, so wait for it
+    # (a fixed head start is not enough where imports are slow)
+    line = standby.stdout.readline()
+    assert line.startswith(b"READY"), (line, standby.stderr.read())
     primary = subprocess.Popen(
         [sys.executable, "-c", _HA_PRIMARY.format(repo=REPO),
          json.dumps(peers)],
