@@ -5,13 +5,15 @@
 void l2_normalize_(at::Tensor x);
 void fill_random_unit_(at::Tensor x, long long row_base, long long seed);
 std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
-                                            long long row_base, int k_out);
+                                            long long row_base, int k_out,
+                                            c10::optional<at::Tensor> allow);
 
 // knn_mfma.hip
 long long knn_bm_value();
 #define KNN_BM_VALUE knn_bm_value()
 std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
-                                            long long row_base, int k_out);
+                                            long long row_base, int k_out,
+                                            c10::optional<at::Tensor> allow);
 
 // gemm.hip
 at::Tensor gemm_nt(at::Tensor a, at::Tensor w, c10::optional<at::Tensor> bias,
@@ -62,10 +64,12 @@ double sync_bench(long long iters, long long which, long long grid,
                   at::Tensor scratch);
 // knn_fp8.hip
 std::tuple<at::Tensor, at::Tensor> knn_fp8(at::Tensor db, at::Tensor q,
-                                           long long row_base, int k_out);
+                                           long long row_base, int k_out,
+                                           c10::optional<at::Tensor> allow);
 std::tuple<at::Tensor, at::Tensor> knn_i8(at::Tensor db, at::Tensor sa,
                                           at::Tensor q, at::Tensor sq,
-                                          long long row_base, int k_out);
+                                          long long row_base, int k_out,
+                                          c10::optional<at::Tensor> allow);
 void decode_tokens(at::Tensor layer_ptrs, at::Tensor x, at::Tensor q,
                    at::Tensor attn, at::Tensor h, at::Tensor rope_cos,
                    at::Tensor rope_sin, at::Tensor embed_w,
@@ -83,14 +87,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fill with deterministic unit-norm pseudo-gaussian rows (bf16)",
         py::arg("x"), py::arg("row_base") = 0, py::arg("seed") = 0x6e6f726eLL);
   m.def("knn_gemv", &knn_gemv,
-        "Fused cosine score + top-k for <=16 queries (bf16 db)",
+        "Fused cosine score + top-k for <=16 queries (bf16 db); allow = "
+        "optional packed int32 row mask (bit r&31 of word r>>5)",
         py::arg("db"), py::arg("q"), py::arg("row_base") = 0,
-        py::arg("k_out") = 10);
+        py::arg("k_out") = 10, py::arg("allow") = c10::nullopt);
   m.attr("KNN_BM") = KNN_BM_VALUE;
   m.def("knn_mfma", &knn_mfma,
         "Fused MFMA cosine score + top-k, 256-query batches (bf16 db)",
         py::arg("db"), py::arg("q"), py::arg("row_base") = 0,
-        py::arg("k_out") = 10);
+        py::arg("k_out") = 10, py::arg("allow") = c10::nullopt);
   m.def("gemm_nt", &gemm_nt,
         "C = A[M,K] @ W[N,K]^T + bias (+GELU), bf16 MFMA 256x256 8-phase",
         py::arg("a"), py::arg("w"), py::arg("bias") = c10::nullopt,
@@ -126,12 +131,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused i8 MFMA score + top-k over a symmetric int8 corpus with "
         "per-row scales (score = i32 dot * sa[row] * sq[col])",
         py::arg("db"), py::arg("sa"), py::arg("q"), py::arg("sq"),
-        py::arg("row_base") = 0, py::arg("k_out") = 10);
+        py::arg("row_base") = 0, py::arg("k_out") = 10,
+        py::arg("allow") = c10::nullopt);
   m.def("knn_fp8", &knn_fp8,
         "Fused MFMA cosine score + top-k over an FP8 e4m3fn corpus "
         "(uint8 carrier), 256-query batches",
         py::arg("db"), py::arg("q"), py::arg("row_base") = 0,
-        py::arg("k_out") = 10);
+        py::arg("k_out") = 10, py::arg("allow") = c10::nullopt);
   m.def("sync_bench", &sync_bench,
         "grid-barrier microbenchmark: ms for `iters` barriers "
         "(which=0 cg::grid.sync, 1 two-level custom)",

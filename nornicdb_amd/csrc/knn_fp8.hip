@@ -20,6 +20,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "allow_mask.h"
 
 #define G_AS __attribute__((address_space(1)))
 #define L_AS __attribute__((address_space(3)))
@@ -35,10 +36,14 @@ __device__ __forceinline__ int swz8(int b) {
   return (b & ~127) | ((b & 127) ^ (((b >> 7) & 7) << 4));
 }
 
+template <bool FILTERED>
 __global__ __launch_bounds__(F8_NTHREADS, 3) void k_knn_fp8(
     const unsigned char* __restrict__ db, const unsigned char* __restrict__ qs,
     long long n_panels, int d, long long row_base,
-    float* __restrict__ cand_score, int* __restrict__ cand_idx) {
+    float* __restrict__ cand_score, int* __restrict__ cand_idx,
+    const unsigned int* __restrict__ allow) {
+  static_assert(!FILTERED || F8_BM % 32 == 0,
+                "filtered kNN needs whole mask words per panel");
   // 44 KB: sA (12 KB) + sB (32 KB); epilogue aliases [256][36] fp32.
   __shared__ __align__(16) char smem[F8_BM * F8_BK + F8_BN * F8_BK];
   unsigned char* sA = (unsigned char*)smem;
@@ -58,6 +63,18 @@ __global__ __launch_bounds__(F8_NTHREADS, 3) void k_knn_fp8(
 
   for (long long panel = blockIdx.x; panel < n_panels; panel += gridDim.x) {
     const long long prow = panel * F8_BM;
+
+    // panel mask words + all-zero panel skip: see k_knn_mfma
+    unsigned int aw[F8_BM / 32];
+    if constexpr (FILTERED) {
+      unsigned int any = 0;
+#pragma unroll
+      for (int h = 0; h < F8_BM / 32; ++h) {
+        aw[h] = allow[(prow >> 5) + h];
+        any |= aw[h];
+      }
+      if (any == 0) continue;
+    }
 
     float4v acc[F8_MW][4];
 #pragma unroll
@@ -139,7 +156,9 @@ __global__ __launch_bounds__(F8_NTHREADS, 3) void k_knn_fp8(
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float s = v[e];
-          if (s > tv[F8_KCAND - 1]) {
+          bool ok = s > tv[F8_KCAND - 1];
+          if constexpr (FILTERED) ok = ok && ((aw[h] >> (j + e)) & 1u);
+          if (ok) {
             float cs = s;
             int ci = (int)(grow0 + j + e);
 #pragma unroll
@@ -175,11 +194,15 @@ __global__ __launch_bounds__(F8_NTHREADS, 3) void k_knn_fp8(
 
 typedef int int4v_ __attribute__((ext_vector_type(4)));
 
+template <bool FILTERED>
 __global__ __launch_bounds__(F8_NTHREADS, 3) void k_knn_i8(
     const signed char* __restrict__ db, const float* __restrict__ sa_g,
     const signed char* __restrict__ qs, const float* __restrict__ sq_g,
     long long n_panels, int d, long long row_base,
-    float* __restrict__ cand_score, int* __restrict__ cand_idx) {
+    float* __restrict__ cand_score, int* __restrict__ cand_idx,
+    const unsigned int* __restrict__ allow) {
+  static_assert(!FILTERED || F8_BM % 32 == 0,
+                "filtered kNN needs whole mask words per panel");
   __shared__ __align__(16) char smem[F8_BM * F8_BK + F8_BN * F8_BK];
   signed char* sA = (signed char*)smem;
   signed char* sB = (signed char*)(smem + F8_BM * F8_BK);
@@ -199,6 +222,18 @@ __global__ __launch_bounds__(F8_NTHREADS, 3) void k_knn_i8(
 
   for (long long panel = blockIdx.x; panel < n_panels; panel += gridDim.x) {
     const long long prow = panel * F8_BM;
+
+    // panel mask words + all-zero panel skip: see k_knn_mfma
+    unsigned int aw[F8_BM / 32];
+    if constexpr (FILTERED) {
+      unsigned int any = 0;
+#pragma unroll
+      for (int h = 0; h < F8_BM / 32; ++h) {
+        aw[h] = allow[(prow >> 5) + h];
+        any |= aw[h];
+      }
+      if (any == 0) continue;
+    }
 
     int4v_ acc[F8_MW][4];
 #pragma unroll
@@ -281,7 +316,9 @@ __global__ __launch_bounds__(F8_NTHREADS, 3) void k_knn_i8(
         for (int e = 0; e < 4; ++e) {
           long long row = grow0 + j + e;
           float s = (float)v[e] * sa_g[row] * sq_own;
-          if (s > tv[F8_KCAND - 1]) {
+          bool ok = s > tv[F8_KCAND - 1];
+          if constexpr (FILTERED) ok = ok && ((aw[h] >> (j + e)) & 1u);
+          if (ok) {
             float cs = s;
             int ci = (int)row;
 #pragma unroll
@@ -387,7 +424,8 @@ __global__ void k_topk_merge_f8(const float* __restrict__ cand_score,
 
 std::tuple<at::Tensor, at::Tensor> knn_i8(at::Tensor db, at::Tensor sa,
                                           at::Tensor q, at::Tensor sq,
-                                          long long row_base, int k_out) {
+                                          long long row_base, int k_out,
+                                          c10::optional<at::Tensor> allow) {
   TORCH_CHECK(db.is_cuda() && db.dim() == 2 && db.is_contiguous() &&
                   db.scalar_type() == at::kChar,
               "knn_i8: db must be contiguous 2D int8 CUDA");
@@ -406,6 +444,8 @@ std::tuple<at::Tensor, at::Tensor> knn_i8(at::Tensor db, at::Tensor sa,
   TORCH_CHECK(n % F8_BM == 0, "knn_i8 needs N % ", F8_BM, " == 0");
   TORCH_CHECK(n < (1LL << 31), "shard too large for int32 local rows");
   TORCH_CHECK(k_out >= 1 && k_out <= F8_KCAND);
+  const unsigned int* allow_p = nullptr;
+  if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "knn_i8");
 
   long long n_panels = n / F8_BM;
   int max_grid = 7680;
@@ -418,12 +458,14 @@ std::tuple<at::Tensor, at::Tensor> knn_i8(at::Tensor db, at::Tensor sa,
   at::Tensor cand_i = at::empty({grid, F8_BN, F8_KCAND},
                                 db.options().dtype(at::kInt));
 
-  hipLaunchKernelGGL(k_knn_i8, dim3(grid), dim3(F8_NTHREADS), 0, stream,
+  auto launch = allow_p ? k_knn_i8<true> : k_knn_i8<false>;
+  hipLaunchKernelGGL(launch, dim3(grid), dim3(F8_NTHREADS), 0, stream,
                      (const signed char*)db.data_ptr(),
                      sa.data_ptr<float>(),
                      (const signed char*)q.data_ptr(),
                      sq.data_ptr<float>(), n_panels, d, row_base,
-                     cand_s.data_ptr<float>(), cand_i.data_ptr<int>());
+                     cand_s.data_ptr<float>(), cand_i.data_ptr<int>(),
+                     allow_p);
   HIP_CHECK_LAST();
 
   at::Tensor out_s = at::empty({F8_BN, k_out}, opts_f);
@@ -438,7 +480,8 @@ std::tuple<at::Tensor, at::Tensor> knn_i8(at::Tensor db, at::Tensor sa,
 }
 
 std::tuple<at::Tensor, at::Tensor> knn_fp8(at::Tensor db, at::Tensor q,
-                                           long long row_base, int k_out) {
+                                           long long row_base, int k_out,
+                                           c10::optional<at::Tensor> allow) {
   TORCH_CHECK(db.is_cuda() && db.dim() == 2 && db.is_contiguous() &&
                   db.scalar_type() == at::kByte,
               "knn_fp8: db must be contiguous 2D uint8 (e4m3fn bits) CUDA");
@@ -453,6 +496,8 @@ std::tuple<at::Tensor, at::Tensor> knn_fp8(at::Tensor db, at::Tensor q,
   TORCH_CHECK(n % F8_BM == 0, "knn_fp8 needs N % ", F8_BM, " == 0");
   TORCH_CHECK(n < (1LL << 31), "shard too large for int32 local rows");
   TORCH_CHECK(k_out >= 1 && k_out <= F8_KCAND);
+  const unsigned int* allow_p = nullptr;
+  if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "knn_fp8");
 
   long long n_panels = n / F8_BM;
   int max_grid = 7680;
@@ -465,11 +510,12 @@ std::tuple<at::Tensor, at::Tensor> knn_fp8(at::Tensor db, at::Tensor q,
   at::Tensor cand_i = at::empty({grid, F8_BN, F8_KCAND},
                                 db.options().dtype(at::kInt));
 
-  hipLaunchKernelGGL(k_knn_fp8, dim3(grid), dim3(F8_NTHREADS), 0, stream,
+  auto launch = allow_p ? k_knn_fp8<true> : k_knn_fp8<false>;
+  hipLaunchKernelGGL(launch, dim3(grid), dim3(F8_NTHREADS), 0, stream,
                      (const unsigned char*)db.data_ptr(),
                      (const unsigned char*)q.data_ptr(), n_panels, d,
                      row_base, cand_s.data_ptr<float>(),
-                     cand_i.data_ptr<int>());
+                     cand_i.data_ptr<int>(), allow_p);
   HIP_CHECK_LAST();
 
   at::Tensor out_s = at::empty({F8_BN, k_out}, opts_f);

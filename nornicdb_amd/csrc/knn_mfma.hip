@@ -28,6 +28,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "allow_mask.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -51,12 +52,18 @@ __device__ __forceinline__ int swz(int b) {
   return (b & ~127) | ((b & 127) ^ (((b >> 7) & 7) << 4));
 }
 
+// FILTERED: `allow` is a packed row mask (bit r&31 of word r>>5 set = local
+// row r may be returned); a panel is BM/32 whole words. FILTERED=false
+// never touches `allow`.
+template <bool FILTERED>
 __global__ __launch_bounds__(NTHREADS, 3) void k_knn_mfma(
     const unsigned short* __restrict__ db, const unsigned short* __restrict__ qs,
     long long n_panels,  // number of full BM-row panels
     int d,               // inner dim, % BK == 0
     long long row_base, float* __restrict__ cand_score,
-    int* __restrict__ cand_idx) {
+    int* __restrict__ cand_idx, const unsigned int* __restrict__ allow) {
+  static_assert(!FILTERED || BM % 32 == 0,
+                "filtered kNN needs whole mask words per panel");
   // 44 KB: K-loop uses sA (12 KB) + sB (32 KB); epilogue reuses the same
   // space as the [256][36] fp32 transposed chunk (36.9 KB).
   __shared__ __align__(16) char smem[BM * BK * 2 + BN * BK * 2];
@@ -78,6 +85,19 @@ __global__ __launch_bounds__(NTHREADS, 3) void k_knn_mfma(
 
   for (long long panel = blockIdx.x; panel < n_panels; panel += gridDim.x) {
     const long long prow = panel * BM;
+
+    // workgroup-uniform mask words of this panel; an all-zero panel is
+    // skipped before any staging (block-uniform, ahead of every barrier)
+    unsigned int aw[(BM + 31) / 32];
+    if constexpr (FILTERED) {
+      unsigned int any = 0;
+#pragma unroll
+      for (int h = 0; h < BM / 32; ++h) {
+        aw[h] = allow[(prow >> 5) + h];
+        any |= aw[h];
+      }
+      if (any == 0) continue;
+    }
 
     float4v acc[MW][4];
 #pragma unroll
@@ -160,7 +180,9 @@ __global__ __launch_bounds__(NTHREADS, 3) void k_knn_mfma(
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float s = v[e];
-          if (s > tv[KCAND - 1]) {
+          bool ok = s > tv[KCAND - 1];
+          if constexpr (FILTERED) ok = ok && ((aw[h] >> (j + e)) & 1u);
+          if (ok) {
             float cs = s;
             int ci = (int)(grow0 + j + e);
 #pragma unroll
@@ -269,7 +291,8 @@ __global__ void k_topk_merge_i32(const float* __restrict__ cand_score,
 // The python side handles the tail rows and q-padding to 256.
 // ---------------------------------------------------------------------------
 std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
-                                            long long row_base, int k_out) {
+                                            long long row_base, int k_out,
+                                            c10::optional<at::Tensor> allow) {
   TORCH_CHECK(db.is_cuda() && db.dim() == 2 && db.is_contiguous() &&
                   db.scalar_type() == at::kBFloat16,
               "knn_mfma: db must be contiguous 2D bf16 CUDA");
@@ -284,6 +307,8 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   TORCH_CHECK(n % BM == 0, "knn_mfma needs N % ", BM, " == 0 (python pads/tails)");
   TORCH_CHECK(n < (1LL << 31), "shard too large for int32 local rows");
   TORCH_CHECK(k_out >= 1 && k_out <= KCAND);
+  const unsigned int* allow_p = nullptr;
+  if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "knn_mfma");
 
   long long n_panels = n / BM;
   // Enough blocks that each retires quickly (load balance + lets other
@@ -305,11 +330,23 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   at::Tensor cand_s = at::empty({grid, BN, KCAND}, opts_f);
   at::Tensor cand_i = at::empty({grid, BN, KCAND}, opts_i32);
 
-  hipLaunchKernelGGL(k_knn_mfma, dim3(grid), dim3(NTHREADS), 0, stream,
-                     (const unsigned short*)db.data_ptr(),
-                     (const unsigned short*)q.data_ptr(), n_panels, d,
-                     row_base, cand_s.data_ptr<float>(),
-                     cand_i.data_ptr<int>());
+  if (allow_p == nullptr) {
+    hipLaunchKernelGGL(k_knn_mfma<false>, dim3(grid), dim3(NTHREADS), 0,
+                       stream, (const unsigned short*)db.data_ptr(),
+                       (const unsigned short*)q.data_ptr(), n_panels, d,
+                       row_base, cand_s.data_ptr<float>(),
+                       cand_i.data_ptr<int>(), allow_p);
+  } else {
+#if KNN_BM % 32 == 0
+    hipLaunchKernelGGL(k_knn_mfma<true>, dim3(grid), dim3(NTHREADS), 0,
+                       stream, (const unsigned short*)db.data_ptr(),
+                       (const unsigned short*)q.data_ptr(), n_panels, d,
+                       row_base, cand_s.data_ptr<float>(),
+                       cand_i.data_ptr<int>(), allow_p);
+#else
+    TORCH_CHECK(false, "knn_mfma: filtered search needs KNN_BM % 32 == 0");
+#endif
+  }
   HIP_CHECK_LAST();
 
   at::Tensor out_s = at::empty({BN, k_out}, opts_f);

@@ -11,6 +11,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "allow_mask.h"
 
 // ---------------------------------------------------------------------------
 // L2 normalize rows, in-place. bf16 [N][D], D % 8 == 0.
@@ -127,16 +128,23 @@ __global__ void k_fill_random_unit_bf16(unsigned short* __restrict__ x,
 // insert). Candidates land in cand[group_global][q][K].
 //
 // Queries are staged in LDS as bf16.
+//
+// FILTERED: `allow` is a packed row mask (allow_mask.h). A group tests its
+// row's bit before touching the row and skips a disallowed row without
+// loading it, so a selective filter saves HBM traffic in proportion. All
+// 16 lanes of a group share the row and take the same branch; the
+// __shfl_xor offsets (< 16) never leave the group.
 // ---------------------------------------------------------------------------
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 
-template <int QMAX, int K>
+template <int QMAX, int K, bool FILTERED>
 __global__ void k_knn_gemv_bf16(const unsigned short* __restrict__ db,
                                 const unsigned short* __restrict__ qs,
                                 long long n, int d, int q_count,
                                 long long row_base,
                                 float* __restrict__ cand_score,
-                                long long* __restrict__ cand_idx) {
+                                long long* __restrict__ cand_idx,
+                                const unsigned int* __restrict__ allow) {
   extern __shared__ unsigned short s_q[];  // [q_count][d]
   const int lane = threadIdx.x & (WAVE - 1);
   const int grp = lane >> 4;        // 4 row-groups per wave
@@ -164,6 +172,9 @@ __global__ void k_knn_gemv_bf16(const unsigned short* __restrict__ db,
   for (int i = 0; i < K; ++i) { tv[i] = -1e30f; ti[i] = -1; }
 
   for (long long row = group_global; row < n; row += total_groups) {
+    if constexpr (FILTERED) {
+      if (!((allow[row >> 5] >> (row & 31)) & 1u)) continue;
+    }
     const unsigned short* rp = db + row * d + (long long)gl * 8;
     float acc[QMAX];
 #pragma unroll
@@ -364,7 +375,8 @@ void fill_random_unit_(at::Tensor x, long long row_base, long long seed) {
 constexpr int KNN_K = 16;
 
 std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
-                                            long long row_base, int k_out) {
+                                            long long row_base, int k_out,
+                                            c10::optional<at::Tensor> allow) {
   TORCH_CHECK(db.is_cuda() && db.dim() == 2 && db.is_contiguous() &&
                   db.scalar_type() == at::kBFloat16,
               "knn_gemv: db must be contiguous 2D bf16 CUDA");
@@ -378,6 +390,8 @@ std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
   TORCH_CHECK(qc >= 1 && qc <= 16, "knn_gemv supports 1..16 queries");
   TORCH_CHECK(d % 128 == 0, "knn_gemv needs D % 128 == 0");
   TORCH_CHECK(k_out >= 1 && k_out <= KNN_K, "k_out must be <= ", KNN_K);
+  const unsigned int* allow_p = nullptr;
+  if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "knn_gemv");
 
   int cap = 1280;
   if (const char* g = getenv("NORNICDB_GEMV_BLOCKS")) cap = atoi(g);
@@ -392,10 +406,13 @@ std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
   size_t lds = (size_t)qc * d * sizeof(unsigned short);
   TORCH_CHECK(lds <= 64 * 1024, "query LDS tile too large");
 
-  hipLaunchKernelGGL((k_knn_gemv_bf16<16, KNN_K>), dim3(blocks), dim3(256),
+  auto launch = allow_p ? k_knn_gemv_bf16<16, KNN_K, true>
+                        : k_knn_gemv_bf16<16, KNN_K, false>;
+  hipLaunchKernelGGL(launch, dim3(blocks), dim3(256),
                      lds, cur_stream(), (const unsigned short*)db.data_ptr(),
                      (const unsigned short*)q.data_ptr(), n, d, qc, row_base,
-                     cand_s.data_ptr<float>(), reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()));
+                     cand_s.data_ptr<float>(), reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()),
+                     allow_p);
   HIP_CHECK_LAST();
 
   at::Tensor out_s = at::empty({qc, k_out}, opts_f);

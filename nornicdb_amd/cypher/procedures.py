@@ -33,7 +33,12 @@ def build_procedures(db: "NornicDB") -> Dict[str, Any]:
             qv = db.embedder.embed_query(query)
         else:
             qv = np.asarray(query, dtype=np.float32)
-        res = db.search.vector_search(qv, int(k))
+        # a registered index searches only nodes of its label (filtered in
+        # the kNN kernel); an unknown index name searches unfiltered
+        from ..search.vectorspace import GLOBAL
+        labels = [s.entity_type for s in GLOBAL.list(db.name)
+                  if s.name == index_name and s.entity_type != "qdrant"]
+        res = db.search.vector_search(qv, int(k), labels=labels or None)
         return ["node", "score"], [[r.node, r.score] for r in res]
 
     @register("db.index.vector.createNodeIndex")

@@ -38,4 +38,6 @@ def native_or_none():
 
 
 from .vector import l2_normalize_, fill_random_unit_  # noqa: E402,F401
-from .knn import knn_search, knn_search_exact  # noqa: E402,F401
+from .knn import (  # noqa: E402,F401
+    knn_search, knn_search_exact, pack_allow_mask, unpack_allow_mask,
+)

@@ -10,12 +10,15 @@ thread per vector and a <<<1,1>>> top-k). Here:
   (96x256 tile, 3 WG/CU, swizzled LDS; csrc/knn_mfma.hip);
 - CPU: exact fp32 torch reference (also the numerics oracle for GPU tests).
 
+Filtered search: every entry point takes an optional `allow` row mask that
+the kernels test before a score can enter the top-k (see pack_allow_mask).
+
 Scores are inner products — callers are expected to store L2-normalized
 vectors for cosine semantics (same contract as the reference,
 pkg/gpu/gpu.go normalized EmbeddingIndex).
 """
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -28,17 +31,87 @@ def _knn_bm() -> int:
     return int(getattr(nat, "KNN_BM", 96)) if nat is not None else 96
 
 
+_NEG_INF = float("-inf")
+
+
+def pack_allow_mask(allow: torch.Tensor) -> torch.Tensor:
+    """bool [N] -> int32 [ceil(N/32)] on the same device.
+
+    Bit (r & 31) of word (r >> 5) is set when local row r (before row_base)
+    may be returned. Bits at positions >= N of the last word are don't-care:
+    no kernel or fallback acts on them."""
+    assert allow.dim() == 1 and allow.dtype == torch.bool
+    n = allow.shape[0]
+    w = (n + 31) // 32
+    bits = torch.zeros(w * 32, dtype=torch.uint8, device=allow.device)
+    bits[:n] = allow
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8,
+                           device=allow.device)
+    # 8 rows -> one byte (byte arithmetic only: 1 B/row of traffic), then 4
+    # bytes -> one little-endian word, byte b holding rows 8b .. 8b+7
+    packed = (bits.view(w * 4, 8) * weights).sum(dim=-1, dtype=torch.uint8)
+    return packed.view(torch.int32)
+
+
+def unpack_allow_mask(words: torch.Tensor, n: int) -> torch.Tensor:
+    """Inverse of pack_allow_mask: int32 words -> bool [n]."""
+    assert words.dim() == 1 and words.dtype == torch.int32
+    assert words.shape[0] * 32 >= n
+    sh = torch.arange(32, device=words.device)
+    bits = (words.to(torch.int64)[:, None] >> sh) & 1
+    return bits.reshape(-1)[:n].bool()
+
+
+def _mask_words(allow: torch.Tensor, n: int) -> torch.Tensor:
+    """Caller's mask (bool [N] or packed int32) -> packed int32 words."""
+    if allow.dtype == torch.bool:
+        assert allow.shape == (n,), "bool allow mask must be [N]"
+        return pack_allow_mask(allow)
+    assert allow.dtype == torch.int32 and allow.dim() == 1 and \
+        allow.shape[0] * 32 >= n, "allow must be bool [N] or int32 [ceil(N/32)]"
+    return allow.contiguous()
+
+
+def _mask_rows(allow: torch.Tensor, start: int, stop: int) -> torch.Tensor:
+    """bool [stop-start] for local rows start..stop of either mask form."""
+    if allow.dtype == torch.bool:
+        return allow[start:stop]
+    w0 = start >> 5
+    sub = unpack_allow_mask(allow[w0:(stop + 31) >> 5], stop - w0 * 32)
+    return sub[start - w0 * 32:]
+
+
+def _masked_topk(scores, ok, kk, base):
+    """top-kk of scores [Q, rows] over the rows with ok set; disallowed
+    picks come back as (-inf, -1), everything else shifted by base."""
+    if ok is not None:
+        scores = scores.masked_fill(~ok, _NEG_INF)
+    s, i = torch.topk(scores, kk, dim=-1)
+    i = i + base
+    if ok is not None:
+        i = i.masked_fill(s == _NEG_INF, -1)
+    return s, i
+
+
+def _pad_unfilled(s, i):
+    """Filtered contract: unfilled slots are (-inf, -1). The kernels leave
+    their -1e30 sentinel with index -1."""
+    return s.masked_fill(i < 0, _NEG_INF), i
+
+
 def knn_search_exact(
-    db: torch.Tensor, q: torch.Tensor, k: int, row_base: int = 0
+    db: torch.Tensor, q: torch.Tensor, k: int, row_base: int = 0,
+    allow: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """fp32 exact reference: returns (scores [Q,k] fp32, indices [Q,k] int64)."""
     scores = q.float() @ db.float().T
-    s, i = torch.topk(scores, k, dim=-1)
-    return s, i + row_base
+    ok = None if allow is None else _mask_rows(allow, 0, db.shape[0])
+    return _masked_topk(scores, ok, k, row_base)
 
 
 def _knn_gemm_chunked(
-    db: torch.Tensor, q: torch.Tensor, k: int, row_base: int, chunk_rows: int = 4 << 20
+    db: torch.Tensor, q: torch.Tensor, k: int, row_base: int,
+    chunk_rows: int = 4 << 20, allow: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Tiled GEMM + top-k. Avoids materializing the full [N, Q] score matrix."""
     n = db.shape[0]
@@ -49,8 +122,8 @@ def _knn_gemm_chunked(
         stop = min(start + chunk_rows, n)
         scores = (qf @ db[start:stop].T).float()  # [Q, chunk]
         kk = min(k, stop - start)
-        s, i = torch.topk(scores, kk, dim=-1)
-        i = i + (row_base + start)
+        ok = None if allow is None else _mask_rows(allow, start, stop)
+        s, i = _masked_topk(scores, ok, kk, row_base + start)
         if best_s is None:
             best_s, best_i = s, i
         else:
@@ -62,32 +135,48 @@ def _knn_gemm_chunked(
 
 
 def knn_search(
-    db: torch.Tensor, q: torch.Tensor, k: int, row_base: int = 0
+    db: torch.Tensor, q: torch.Tensor, k: int, row_base: int = 0,
+    allow: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k inner-product search of q (Q x D) against db (N x D).
 
     db may be bf16 or float8_e4m3fn (opt-in quantized corpus — half the
     HBM traffic, 2x capacity; scored by the fp8 MFMA kernel on GPU).
     Returns (scores [Q,k] fp32, global indices [Q,k] int64).
+
+    allow: optional row filter shared by all queries — a bool [N] tensor or
+    a packed int32 mask (pack_allow_mask) on db's device. With m allowed
+    rows the first min(k, m) slots hold the allowed top scores in
+    descending order; every remaining slot is (score -inf, index -1).
     """
     assert db.dim() == 2 and q.dim() == 2 and db.shape[1] == q.shape[1]
     k = min(k, db.shape[0])
+    if allow is None:
+        return _knn_dispatch(db, q, k, row_base, None)
+    assert allow.device == db.device, "allow mask must live on db's device"
+    if db.is_cuda:
+        allow = _mask_words(allow, db.shape[0])
+    return _pad_unfilled(*_knn_dispatch(db, q, k, row_base, allow))
+
+
+def _knn_dispatch(db, q, k, row_base, allow):
+    """Q/k/dtype routing; allow is None or (on GPU) packed mask words."""
     if not db.is_cuda:
-        return knn_search_exact(db, q, k, row_base)
+        return knn_search_exact(db, q, k, row_base, allow)
     if db.dtype == torch.float8_e4m3fn:
         nat = native_or_none()
         if nat is None:
             require_native()
         if k <= 10 and db.shape[1] % 128 == 0 and db.shape[0] >= 96:
             if q.shape[0] <= 256:
-                return _knn_fp8(nat, db, q, k, row_base)
+                return _knn_fp8(nat, db, q, k, row_base, allow)
             ss, ii = [], []
             for s in range(0, q.shape[0], 256):
-                cs, ci = _knn_fp8(nat, db, q[s:s + 256], k, row_base)
+                cs, ci = _knn_fp8(nat, db, q[s:s + 256], k, row_base, allow)
                 ss.append(cs)
                 ii.append(ci)
             return torch.cat(ss, 0), torch.cat(ii, 0)
-        return _knn_fp8_chunked(db, q, k, row_base)
+        return _knn_fp8_chunked(db, q, k, row_base, allow=allow)
 
     nat = native_or_none()
     if nat is None:
@@ -102,7 +191,7 @@ def knn_search(
         and db.shape[1] % 128 == 0
     ):
         qq = q.to(torch.bfloat16).contiguous()
-        return nat.knn_gemv(db.contiguous(), qq, row_base, k)
+        return nat.knn_gemv(db.contiguous(), qq, row_base, k, allow)
     if (
         k <= 10
         and db.dtype == torch.bfloat16
@@ -110,12 +199,12 @@ def knn_search(
         and db.shape[0] >= _knn_bm()
     ):
         if q.shape[0] <= 256:
-            return _knn_mfma(nat, db, q, k, row_base)
+            return _knn_mfma(nat, db, q, k, row_base, allow)
         # large query batches (multi-GPU all-gather): chunk through the
         # fused kernel 256 queries at a time
         ss, ii = [], []
         for s in range(0, q.shape[0], 256):
-            cs, ci = _knn_mfma(nat, db, q[s:s + 256], k, row_base)
+            cs, ci = _knn_mfma(nat, db, q[s:s + 256], k, row_base, allow)
             ss.append(cs)
             ii.append(ci)
         return torch.cat(ss, 0), torch.cat(ii, 0)
@@ -128,8 +217,8 @@ def knn_search(
         # Q 9..16 with k 11..16: MFMA path capped at k<=10, gemv still wins
         # over the chunked-GEMM fallback at these batch sizes
         qq = q.to(torch.bfloat16).contiguous()
-        return nat.knn_gemv(db.contiguous(), qq, row_base, k)
-    return _knn_gemm_chunked(db, q, k, row_base)
+        return nat.knn_gemv(db.contiguous(), qq, row_base, k, allow)
+    return _knn_gemm_chunked(db, q, k, row_base, allow=allow)
 
 
 def quantize_fp8(db: torch.Tensor) -> torch.Tensor:
@@ -151,20 +240,31 @@ def quantize_int8(db: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 
 def knn_search_int8(
     db: torch.Tensor, sa: torch.Tensor, q: torch.Tensor, k: int,
-    row_base: int = 0,
+    row_base: int = 0, allow: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k over a symmetric int8 corpus (per-row scales sa).
 
     q is float (bf16/f32); it is int8-quantized internally so GPU main
     panels and the tail score identical values. i32 dots are exact in
-    fp32 up to d*127^2 < 2^24 (d <= 1024)."""
+    fp32 up to d*127^2 < 2^24 (d <= 1024).
+
+    allow: optional row filter, same forms and contract as knn_search."""
     assert db.dtype == torch.int8 and db.dim() == 2
     k = min(k, db.shape[0])
+    if allow is None:
+        return _knn_int8_dispatch(db, sa, q, k, row_base, None)
+    assert allow.device == db.device, "allow mask must live on db's device"
+    if db.is_cuda:
+        allow = _mask_words(allow, db.shape[0])
+    return _pad_unfilled(*_knn_int8_dispatch(db, sa, q, k, row_base, allow))
+
+
+def _knn_int8_dispatch(db, sa, q, k, row_base, allow):
     qi, sq = quantize_int8(q)
     if not db.is_cuda:
         scores = (qi.float() * sq[:, None]) @ (db.float() * sa[:, None]).T
-        s, i = torch.topk(scores, k, dim=-1)
-        return s, i + row_base
+        ok = None if allow is None else _mask_rows(allow, 0, db.shape[0])
+        return _masked_topk(scores, ok, k, row_base)
     nat = native_or_none()
     if nat is None:
         require_native()
@@ -172,7 +272,8 @@ def knn_search_int8(
         if q.shape[0] > 256:
             ss, ii = [], []
             for s0 in range(0, q.shape[0], 256):
-                cs, ci = knn_search_int8(db, sa, q[s0:s0 + 256], k, row_base)
+                cs, ci = _knn_int8_dispatch(db, sa, q[s0:s0 + 256], k,
+                                            row_base, allow)
                 ss.append(cs)
                 ii.append(ci)
             return torch.cat(ss, 0), torch.cat(ii, 0)
@@ -187,7 +288,7 @@ def knn_search_int8(
         s, i = nat.knn_i8(db.narrow(0, 0, n_main).contiguous(),
                           sa.narrow(0, 0, n_main).contiguous().float(),
                           qi.contiguous(), sq.contiguous().float(),
-                          row_base, k)
+                          row_base, k, allow)
         s, i = s[:qn], i[:qn]
         if n_main < n:
             tail = db.narrow(0, n_main, n - n_main)
@@ -195,8 +296,8 @@ def knn_search_int8(
             ts = (qi[:qn].float() * sq[:qn, None]) @ \
                  (tail.float() * tsa[:, None]).T
             kk = min(k, n - n_main)
-            bs, bi = torch.topk(ts, kk, dim=-1)
-            bi = bi + (row_base + n_main)
+            ok = None if allow is None else _mask_rows(allow, n_main, n)
+            bs, bi = _masked_topk(ts, ok, kk, row_base + n_main)
             cs = torch.cat([s, bs], -1)
             ci = torch.cat([i, bi], -1)
             s, sel = torch.topk(cs, k, dim=-1)
@@ -211,8 +312,8 @@ def knn_search_int8(
         chunk = (db[start:stop].float() * sa[start:stop, None]).to(torch.bfloat16)
         scores = (qf @ chunk.T).float()
         kk = min(k, stop - start)
-        s, i = torch.topk(scores, kk, dim=-1)
-        i = i + (row_base + start)
+        ok = None if allow is None else _mask_rows(allow, start, stop)
+        s, i = _masked_topk(scores, ok, kk, row_base + start)
         if best_s is None:
             best_s, best_i = s, i
         else:
@@ -223,7 +324,7 @@ def knn_search_int8(
     return best_s, best_i
 
 
-def _knn_fp8(nat, db, q, k, row_base):
+def _knn_fp8(nat, db, q, k, row_base, allow=None):
     """Fused fp8 MFMA score+topk over full 96-row panels + torch tail.
 
     q is quantized to e4m3fn so main-panel and tail scores agree
@@ -238,14 +339,14 @@ def _knn_fp8(nat, db, q, k, row_base):
     n = db.shape[0]
     n_main = (n // 96) * 96
     s, i = nat.knn_fp8(db.narrow(0, 0, n_main).view(torch.uint8), qu,
-                       row_base, k)
+                       row_base, k, allow)
     s, i = s[:qn], i[:qn]
     if n_main < n:
         tail = db.narrow(0, n_main, n - n_main).to(torch.bfloat16)
         ts = (q8[:qn].to(torch.bfloat16) @ tail.T).float()
         kk = min(k, n - n_main)
-        bs, bi = torch.topk(ts, kk, dim=-1)
-        bi = bi + (row_base + n_main)
+        ok = None if allow is None else _mask_rows(allow, n_main, n)
+        bs, bi = _masked_topk(ts, ok, kk, row_base + n_main)
         cs = torch.cat([s, bs], -1)
         ci = torch.cat([i, bi], -1)
         s, sel = torch.topk(cs, k, dim=-1)
@@ -253,7 +354,8 @@ def _knn_fp8(nat, db, q, k, row_base):
     return s, i
 
 
-def _knn_fp8_chunked(db, q, k, row_base, chunk_rows: int = 4 << 20):
+def _knn_fp8_chunked(db, q, k, row_base, chunk_rows: int = 4 << 20,
+                     allow=None):
     """Dequantize-per-chunk fallback (k > 10 or odd dims)."""
     n = db.shape[0]
     qf = q.to(torch.bfloat16)
@@ -262,8 +364,8 @@ def _knn_fp8_chunked(db, q, k, row_base, chunk_rows: int = 4 << 20):
         stop = min(start + chunk_rows, n)
         scores = (qf @ db[start:stop].to(torch.bfloat16).T).float()
         kk = min(k, stop - start)
-        s, i = torch.topk(scores, kk, dim=-1)
-        i = i + (row_base + start)
+        ok = None if allow is None else _mask_rows(allow, start, stop)
+        s, i = _masked_topk(scores, ok, kk, row_base + start)
         if best_s is None:
             best_s, best_i = s, i
         else:
@@ -274,7 +376,7 @@ def _knn_fp8_chunked(db, q, k, row_base, chunk_rows: int = 4 << 20):
     return best_s, best_i
 
 
-def _knn_mfma(nat, db, q, k, row_base):
+def _knn_mfma(nat, db, q, k, row_base, allow=None):
     """Fused MFMA score+topk over full BM-row panels + torch-scored tail."""
     qn = q.shape[0]
     qq = q.to(torch.bfloat16)
@@ -286,14 +388,14 @@ def _knn_mfma(nat, db, q, k, row_base):
     n = db.shape[0]
     bm = _knn_bm()
     n_main = (n // bm) * bm
-    s, i = nat.knn_mfma(db.narrow(0, 0, n_main), qq, row_base, k)
+    s, i = nat.knn_mfma(db.narrow(0, 0, n_main), qq, row_base, k, allow)
     s, i = s[:qn], i[:qn]
     if n_main < n:
         tail = db.narrow(0, n_main, n - n_main)
         ts = (qq[:qn] @ tail.T).float()
         kk = min(k, n - n_main)
-        bs, bi = torch.topk(ts, kk, dim=-1)
-        bi = bi + (row_base + n_main)
+        ok = None if allow is None else _mask_rows(allow, n_main, n)
+        bs, bi = _masked_topk(ts, ok, kk, row_base + n_main)
         cs = torch.cat([s, bs], -1)
         ci = torch.cat([i, bi], -1)
         s, sel = torch.topk(cs, k, dim=-1)

@@ -9,7 +9,7 @@ the fused HIP kNN kernels (ops.knn_search). No multi-backend probing.
 from __future__ import annotations
 
 import threading
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -46,6 +46,13 @@ class EmbeddingIndex:
         self._ids: List[str] = []
         self._id2slot: Dict[str, int] = {}
         self._dead: set = set()
+        # host-side bit per slot: set while the slot holds a live vector.
+        # Searches pass it (ANDed with any allow_ids filter) to the kNN
+        # kernels as the allow-mask, so tombstones never widen k. The
+        # device copy is re-packed lazily on the next search after a change.
+        self._live = np.zeros(capacity, dtype=bool)
+        self._live_dirty = True
+        self._live_words: Optional[torch.Tensor] = None
 
     def __len__(self):
         return self._n - len(self._dead)
@@ -62,6 +69,9 @@ class EmbeddingIndex:
             ns = torch.zeros(new_cap, device=self.device)
             ns[:self._n] = self._scales[:self._n]
             self._scales = ns
+        nl = np.zeros(new_cap, dtype=bool)
+        nl[:self._n] = self._live[:self._n]
+        self._live = nl
 
     @staticmethod
     def _normalize(t: torch.Tensor) -> torch.Tensor:
@@ -86,6 +96,7 @@ class EmbeddingIndex:
                 if sc is not None:
                     self._scales[slot] = sc[0]
                 self._dead.discard(slot)
+                self._set_live(slot, True)
                 return
             self._grow(self._n + 1)
             self._buf[self._n] = v[0]
@@ -93,6 +104,7 @@ class EmbeddingIndex:
                 self._scales[self._n] = sc[0]
             self._ids.append(id_)
             self._id2slot[id_] = self._n
+            self._set_live(self._n, True)
             self._n += 1
 
     def add_batch(self, ids: Sequence[str], mat) -> None:
@@ -107,12 +119,14 @@ class EmbeddingIndex:
                     if sc is not None:
                         self._scales[slot] = sc[i]
                     self._dead.discard(slot)
+                    self._set_live(slot, True)
                 else:
                     self._buf[self._n] = m[i]
                     if sc is not None:
                         self._scales[self._n] = sc[i]
                     self._ids.append(id_)
                     self._id2slot[id_] = self._n
+                    self._set_live(self._n, True)
                     self._n += 1
 
     def remove(self, id_: str) -> bool:
@@ -121,25 +135,67 @@ class EmbeddingIndex:
             if slot is None:
                 return False
             self._dead.add(slot)
+            self._set_live(slot, False)
             return True
 
-    def search(self, query, k: int) -> List[Tuple[str, float]]:
-        """Brute-force top-k over all vectors (fused HIP kernel on GPU)."""
+    def _set_live(self, slot: int, on: bool):
+        self._live[slot] = on
+        self._live_dirty = True
+
+    def _allow_mask(self, allow_ids: Optional[Iterable[str]]):
+        """Packed allow-mask for the next kNN call, or None when every slot
+        may be returned (no tombstones, no filter)."""
+        if allow_ids is None:
+            if not self._dead:
+                return None
+            if self._live_dirty:
+                self._live_words = self._upload_mask(self._live[:self._n])
+                self._live_dirty = False
+            return self._live_words
+        # live & allow_ids: _id2slot only knows live ids, unknown ids drop out
+        ok = np.zeros(self._n, dtype=bool)
+        slots = [self._id2slot[i] for i in allow_ids if i in self._id2slot]
+        ok[slots] = True
+        return self._upload_mask(ok)
+
+    def _upload_mask(self, ok: np.ndarray) -> torch.Tensor:
+        """Host bool per slot -> packed words on the device (packed on the
+        host, so 1 bit per slot crosses the bus)."""
+        from ..ops.knn import pack_allow_mask
+
+        return pack_allow_mask(torch.from_numpy(ok)).to(self.device)
+
+    def _knn(self, q: torch.Tensor, k: int, allow_ids):
         from ..ops import knn_search
 
+        kk = min(k, self._n)
+        mask = self._allow_mask(allow_ids)
+        if self.quant == "int8":
+            from ..ops.knn import knn_search_int8
+            if mask is None:
+                return knn_search_int8(self._buf[:self._n],
+                                       self._scales[:self._n], q, kk)
+            return knn_search_int8(self._buf[:self._n],
+                                   self._scales[:self._n], q, kk, allow=mask)
+        if mask is None:
+            return knn_search(self._buf[:self._n], q.to(self.dtype), kk)
+        return knn_search(self._buf[:self._n], q.to(self.dtype), kk,
+                          allow=mask)
+
+    def search(self, query, k: int,
+               allow_ids: Optional[Iterable[str]] = None
+               ) -> List[Tuple[str, float]]:
+        """Brute-force top-k over all vectors (fused HIP kernel on GPU).
+
+        allow_ids restricts the hits to those ids (unknown ids are
+        ignored); the filter runs inside the kNN kernel."""
         with self._lock:
             if self._n == 0:
                 return []
             q = torch.as_tensor(np.asarray(query, dtype=np.float32),
                                 device=self.device).reshape(1, -1)
             q = self._normalize(q)
-            kk = min(k + len(self._dead), self._n)
-            if self.quant == "int8":
-                from ..ops.knn import knn_search_int8
-                s, i = knn_search_int8(self._buf[:self._n],
-                                       self._scales[:self._n], q, kk)
-            else:
-                s, i = knn_search(self._buf[:self._n], q.to(self.dtype), kk)
+            s, i = self._knn(q, k, allow_ids)
             out = []
             for score, slot in zip(s[0].tolist(), i[0].tolist()):
                 if slot < 0 or slot in self._dead:
@@ -149,22 +205,16 @@ class EmbeddingIndex:
                     break
             return out
 
-    def search_batch(self, queries, k: int) -> List[List[Tuple[str, float]]]:
-        from ..ops import knn_search
-
+    def search_batch(self, queries, k: int,
+                     allow_ids: Optional[Iterable[str]] = None
+                     ) -> List[List[Tuple[str, float]]]:
         with self._lock:
             if self._n == 0:
                 return [[] for _ in range(len(queries))]
             q = torch.as_tensor(np.asarray(queries, dtype=np.float32),
                                 device=self.device)
             q = self._normalize(q)
-            kk = min(k + len(self._dead), self._n)
-            if self.quant == "int8":
-                from ..ops.knn import knn_search_int8
-                s, i = knn_search_int8(self._buf[:self._n],
-                                       self._scales[:self._n], q, kk)
-            else:
-                s, i = knn_search(self._buf[:self._n], q.to(self.dtype), kk)
+            s, i = self._knn(q, k, allow_ids)
             outs = []
             for r in range(q.shape[0]):
                 out = []

@@ -8,7 +8,7 @@ vectors (:22-24), HNSW in the mid range, k-means cluster routing above
 
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import Iterable, List, Optional, Tuple
 
 from .embedding_index import EmbeddingIndex
 from .hnsw import HNSWIndex
@@ -29,23 +29,39 @@ class VectorSearchPipeline:
         self.hnsw = hnsw
         self.clusters = clusters
 
-    def search(self, query, k: int) -> List[Tuple[str, float]]:
+    def search(self, query, k: int,
+               allow_ids: Optional[Iterable[str]] = None
+               ) -> List[Tuple[str, float]]:
+        """allow_ids restricts hits to those ids: the brute-force branches
+        filter inside the kNN kernel; the HNSW and cluster branches
+        intersect their candidates with it and fall back to the filtered
+        brute-force search when fewer than k survive."""
         n = len(self.emb)
         if n == 0:
             return []
+        if allow_ids is not None and not isinstance(allow_ids, (set, frozenset)):
+            allow_ids = set(allow_ids)
         # brute force: small corpora, or GPU path (fused kernel IS the fast path)
         if n <= BRUTE_MAX or (self.emb.device.type == "cuda"
                               and (self.clusters is None or self.clusters.k == 0)):
-            return self.emb.search(query, k)
+            return self.emb.search(query, k, allow_ids=allow_ids)
         if n > KMEANS_MIN and self.clusters is not None and self.clusters.k > 0:
             cands = self.clusters.candidates(query)
             if len(cands) > candidate_count(k):
                 # HNSW narrows within the routed set if available, else truncate
                 cands = cands[: candidate_count(k) * 4]
+            if allow_ids is not None:
+                cands = [i for i in cands if i in allow_ids]
+                if len(cands) < k:
+                    return self.emb.search(query, k, allow_ids=allow_ids)
             scored = self.emb.score_subset(query, cands)
             return scored[:k]
         if self.hnsw is not None and len(self.hnsw) > 0:
             cands = [i for i, _ in self.hnsw.search(query, candidate_count(k))]
+            if allow_ids is not None:
+                cands = [i for i in cands if i in allow_ids]
+                if len(cands) < k:
+                    return self.emb.search(query, k, allow_ids=allow_ids)
             scored = self.emb.score_subset(query, cands)
             return scored[:k]
-        return self.emb.search(query, k)
+        return self.emb.search(query, k, allow_ids=allow_ids)

@@ -61,6 +61,10 @@ class SearchService:
         self.hnsw = HNSWIndex(dims) if use_hnsw else None
         self.clusters = ClusterIndex()
         self.pipeline = VectorSearchPipeline(self.emb, self.hnsw, self.clusters)
+        # label -> ids of nodes with an embedding; the vector path turns a
+        # label predicate into the kNN allow-mask instead of over-fetching
+        self._label_ids: Dict[str, set] = {}
+        self._node_labels: Dict[str, Tuple[str, ...]] = {}
         engine.register_callback(self._on_event)
 
     # ---- storage sync ----
@@ -75,7 +79,13 @@ class SearchService:
             text = node_text(node)
             if text:
                 self.fulltext.index(node.id, text)
-            if node.embedding is not None and len(node.embedding) == self.dims:
+            has_vec = (node.embedding is not None
+                       and len(node.embedding) == self.dims)
+            if has_vec or node.id in self._node_labels:
+                # also on an update that carries no embedding: the vector
+                # indexed earlier stays searchable under the new labels
+                self._set_labels(node.id, node.labels)
+            if has_vec:
                 self.emb.add(node.id, node.embedding)
                 if self.hnsw is not None and len(self.emb) <= KMEANS_MIN:
                     self.hnsw.add(node.id, node.embedding)
@@ -84,10 +94,38 @@ class SearchService:
     def remove_node(self, node_id: str):
         with self._lock:
             self.fulltext.remove(node_id)
+            self._set_labels(node_id, ())
+            self._node_labels.pop(node_id, None)
             self.emb.remove(node_id)
             if self.hnsw is not None:
                 self.hnsw.remove(node_id)
             self.clusters.remove(node_id)
+
+    def _set_labels(self, node_id: str, labels: Sequence[str]):
+        """Move node_id into exactly the sets of `labels` (a NODE_UPDATED
+        that changes labels leaves the old sets)."""
+        new = tuple(labels or ())
+        old = self._node_labels.get(node_id, ())
+        for lb in old:
+            if lb not in new:
+                ids = self._label_ids.get(lb)
+                if ids is not None:
+                    ids.discard(node_id)
+                    if not ids:
+                        del self._label_ids[lb]
+        for lb in new:
+            self._label_ids.setdefault(lb, set()).add(node_id)
+        self._node_labels[node_id] = new
+
+    def _allow_ids(self, labels: Sequence[str]) -> Optional[set]:
+        """Union of the label sets, or None without a label predicate."""
+        if not labels:
+            return None
+        with self._lock:
+            out: set = set()
+            for lb in labels:
+                out |= self._label_ids.get(lb, set())
+            return out
 
     def build_indexes(self):
         """Full scan (reference BuildIndexes)."""
@@ -107,8 +145,8 @@ class SearchService:
     # ---- queries ----
     def vector_search(self, query_vec, k: int = 10,
                       labels: Sequence[str] = None) -> List[SearchResult]:
-        hits = self.pipeline.search(np.asarray(query_vec, np.float32), k * 3
-                                    if labels else k)
+        hits = self.pipeline.search(np.asarray(query_vec, np.float32), k,
+                                    allow_ids=self._allow_ids(labels))
         return self._materialize(hits, k, labels, source="vector")
 
     def text_search(self, query: str, k: int = 10,
@@ -127,7 +165,8 @@ class SearchService:
             rankings.append(self.fulltext.search(query, max(k * 4, 40)))
         if query_vec is not None and len(self.emb) > 0:
             rankings.append(self.pipeline.search(
-                np.asarray(query_vec, np.float32), max(k * 4, 40)))
+                np.asarray(query_vec, np.float32), max(k * 4, 40),
+                allow_ids=self._allow_ids(labels)))
         if not rankings:
             return []
         if len(rankings) == 1:

@@ -306,7 +306,8 @@ def qdrant_router(registry: QdrantRegistry = None) -> APIRouter:
             raise HTTPException(400, "vector required")
         limit = int(body.get("limit", 10))
         with_payload = body.get("with_payload", True)
-        hits = c.index.search(vec, limit)
+        hits = c.index.search(vec, limit,
+                              allow_ids=_allowed_ids(c, body.get("filter")))
         out = []
         for pid, score in hits:
             item = {"id": _maybe_int(pid), "version": 0, "score": score}
@@ -448,14 +449,17 @@ def qdrant_router(registry: QdrantRegistry = None) -> APIRouter:
         limit = int(body.get("limit", 10))
         if isinstance(q, dict) and "nearest" in q:
             q = q["nearest"]
+        flt = body.get("filter")
+        # the filter is evaluated inside the kNN kernel (allow-mask), so
+        # `limit` hits are enough however selective it is
         if isinstance(q, list):            # vector query
-            hits = c.index.search(q, limit * 4)
+            hits = c.index.search(q, limit, allow_ids=_allowed_ids(c, flt))
         elif q is not None and str(q) in c.vectors:  # by point id
-            hits = c.index.search(c.vectors[str(q)], limit * 4 + 1)
+            hits = c.index.search(c.vectors[str(q)], limit + 1,
+                                  allow_ids=_allowed_ids(c, flt))
             hits = [(p, s) for p, s in hits if p != str(q)]
         else:
             hits = [(pid, 1.0) for pid in sorted(c.payloads)][:limit * 4]
-        flt = body.get("filter")
         out = []
         for pid, score in hits:
             if flt and not _matches(c.payloads.get(pid, {}), flt):
@@ -564,6 +568,14 @@ def _matches(payload: Dict[str, Any], flt: Dict[str, Any]) -> bool:
     if should and not any(cond_ok(c) for c in should):
         return False
     return True
+
+
+def _allowed_ids(c: "_Collection", flt: Optional[Dict[str, Any]]):
+    """Point ids whose payload passes the filter (None = no filter), for
+    EmbeddingIndex.search(allow_ids=...)."""
+    if not flt:
+        return None
+    return [pid for pid, pl in c.payloads.items() if _matches(pl, flt)]
 
 
 def _maybe_int(pid):

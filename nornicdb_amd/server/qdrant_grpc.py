@@ -26,7 +26,7 @@ from typing import Dict, List
 import grpc
 from google.protobuf import descriptor_pb2, descriptor_pool, message_factory
 
-from .qdrant import QdrantRegistry, _matches, _maybe_int
+from .qdrant import QdrantRegistry, _allowed_ids, _matches, _maybe_int
 
 _T = descriptor_pb2.FieldDescriptorProto
 _PKG = "qdrant"
@@ -523,7 +523,8 @@ class QdrantGrpc:
     def _search_one(self, c, req):
         limit = int(req.limit) or 10
         flt = _filter_to_json(req.filter)
-        hits = c.index.search(list(req.vector), limit * 4 if flt else limit)
+        hits = c.index.search(list(req.vector), limit,
+                              allow_ids=_allowed_ids(c, flt))
         out = []
         for pid, score in hits:
             if flt and not _matches(c.payloads.get(pid, {}), flt):
