@@ -5,28 +5,74 @@
 // [N, Q] score matrix is never materialized in HBM. The DB shard is read
 // exactly once per query batch.
 //
-// Structure (chosen by ablation, scripts/knn8p.hip — see profiles/README.md):
-//   * 96x256 output tile, 4 waves (256 thr), 3 workgroups/CU. Occupancy is
-//     the LDS-DMA throughput lever on gfx950: global_load_lds ingest
-//     scales with resident waves (1-WG/8-wave kernels cap at ~3 TB/s
-//     aggregate DMA; 12 waves across 3 WGs reach ~8.8 TB/s), so the
-//     "big-tile 1-WG pipelined" template loses to 3 small co-resident WGs.
-//   * row-XOR LDS swizzle: 16-B slot index XORed with (row & 7) inside
-//     each 128-B row; kills the 16-way ds_read bank conflict of
-//     16-consecutive-rows-at-one-column fragment reads (measured:
-//     SQ_LDS_BANK_CONFLICT -> 0, +9% kernel).
-//   * mfma_f32_16x16x32_bf16 fragments, BK=64 K-steps, staging via
-//     __builtin_amdgcn_global_load_lds width 16.
-//   * transposed epilogue: acc fragments land in a [col][36] fp32 LDS
-//     chunk with float4 stores/scans (4 consecutive rows per C-register
-//     quad); each thread owns one query column and keeps a register
-//     top-K list (statically unrolled insertion).
+// Structure (history of the measurements: profiles/README.md):
+//   * 160x256 output tile, 4 waves (256 thr), 2 workgroups/CU (62 KB LDS,
+//     233 VGPRs, no spills). The kernel is bound by what a CU can ingest:
+//     every corpus byte (HBM) drags 256*2/BM bytes of query tile (L2)
+//     through the same load path, 2.67 B at 96 rows and 1.6 B at 160.
+//     Taller tiles are what buys speed; the software pipeline below is
+//     what lets two workgroups per CU keep that path busy, where the
+//     synchronous loop needed three co-resident ones to overlap at all.
+//   * one flat stream of BK=32 stages per workgroup: the (panel, k) loops
+//     are flattened, stage g = (panel, 32-wide K slice). Per stage a wave
+//     runs 40 mfma_f32_16x16x32_bf16 (ascending k per accumulator, the
+//     same order as a BK=64 loop, so scores do not depend on the staging).
+//   * LDS: query tile double-buffered (2 x 16 KB), corpus tile in a ring of
+//     three 10 KB buffers; staged by __builtin_amdgcn_global_load_lds width
+//     16. While stage g computes, the queries of stage g+1 (L2-resident)
+//     and the corpus rows of stages g+1 and g+2 (the HBM stream) are in
+//     flight; the corpus prefetch crosses the panel boundary, so it also
+//     runs under the top-k epilogue.
+//   * stage rows are 64 B; 16 B-slot XOR swizzle, applied to the global
+//     source address and to the ds_read address (see swz()).
+//   * fragment reads and the epilogue's LDS traffic are inline asm with
+//     explicit lgkmcnt waits and raw s_barrier: with compiler-visible LDS
+//     accesses or __syncthreads() hipcc waits vmcnt(0) while an LDS-DMA is
+//     outstanding and the prefetch drains every stage.
+//   * transposed epilogue: acc fragments go 16 rows at a time through a
+//     [col][16] fp32 block that lives in the query buffer the last stage
+//     just read (the other one is receiving the next stage's queries);
+//     each thread owns one query column and keeps a register top-K list
+//     (statically unrolled insertion).
+//   * corpus loads use the default cache policy: non-temporal (aux = 2)
+//     measured 22 % slower (81.8 vs 67.1 ms at 100M rows, 96-row tile).
+//   KNN_BM=96 builds the same kernel at 3 workgroups/CU (50 KB LDS, 161
+//   VGPRs); it measured within 2 % of the synchronous 96-row loop.
+//
+// Pipeline ordering (VM loads retire in order; counts are per wave):
+//   stage g issues  B(g+1)  NB = 4 instructions   -> sB[(g+1)&1]
+//          then     A(g+2)  NA = 3 instructions   -> sA[(g+2)%3]
+//   (NB = 256 query rows / 16 rows per 1 KB piece / 4 waves; NA = BM/16
+//   pieces over 4 waves: 10 pieces = 2 whole + 1 half piece per wave)
+//   and ends with   s_waitcnt vmcnt(NA); s_barrier.
+//   At that wait the wave's queue holds, oldest first,
+//     A(g+1) [issued in stage g-1, after B(g)], B(g+1), A(g+2),
+//   everything older having been retired by stage g-1's wait. vmcnt(NA)
+//   therefore retires A(g+1) and B(g+1) and leaves only A(g+2) in flight.
+//   An A(g+1)-before-B(g) order would need a wait that also drains the
+//   newest prefetch; issuing the prefetch LAST is what keeps it in flight.
+//   Read-after-DMA: stage g+1 reads sB[(g+1)&1] and sA[(g+1)%3] after the
+//   barrier that follows that wait in every wave, so every wave's pieces
+//   have landed. Write-after-read: B(g+1) and A(g+2) overwrite the buffers
+//   stage g-1 read; every wave retired those ds_reads (lgkmcnt(0) ahead of
+//   its last MFMA group) before it arrived at stage g-1's end barrier.
+//   The epilogue block reuses sB[g&1] after stage g's end barrier and is
+//   followed by a barrier of its own before stage g+1 restages that buffer;
+//   no DMA targets sB[g&1] in between (B(g+1) went to the other buffer,
+//   A lives in its own ring).
+//   The filtered kernel finds the next panel with an allowed row before
+//   the stage loop of the current one, so a skipped panel never enters the
+//   stream: buffer rotation and outstanding-load counts do not see it.
+//   At the end of the stream the prefetches are still issued (from the
+//   current panel's rows, never used) to keep the counts uniform, and a
+//   vmcnt(0) ahead of the candidate write-out retires them.
 //
 // Replaces the reference's cublasSgemv + single-thread top-k scan
 // (reference: pkg/gpu/cuda/cuda_kernels.cu:340-480).
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <type_traits>
 #include "common.h"
 #include "allow_mask.h"
 
@@ -37,43 +83,107 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // tile geometry
 #ifndef KNN_BM
-#define KNN_BM 96
+#define KNN_BM 160
 #endif
 #define BM KNN_BM
 #define BN 256
-#define BK 64
+#define BK 32  // K extent of one pipeline stage
 #define NTHREADS 256
 #define KCAND 10
 #define MW (BM / 16)
 
-// row-XOR swizzle (self-inverse): within a 128 B row, XOR the 16 B-slot
-// index with (row & 7).
+#define SB_BYTES (BN * BK * 2)  // one query stage: 16 KB
+#define SA_BYTES (BM * BK * 2)  // one corpus stage: 10 KB at BM=160
+#define SMEM_BYTES (2 * SB_BYTES + 3 * SA_BYTES)
+
+// LDS-DMA instructions per wave per stage. A stage is BM/16 pieces of 1 KB
+// (16 rows x 64 B); each wave stages A_FULL whole pieces and, when the
+// piece count is 2 mod 4, one half piece (8 rows, lanes 0-31).
+#define A_PIECES (BM / 16)
+#define A_FULL (A_PIECES / 4)
+#define A_HALF (A_PIECES % 4 == 2 ? 1 : 0)
+#define NA (A_FULL + A_HALF)
+#define NB (BN / 16 / 4)
+static_assert(A_PIECES % 4 == 0 || A_PIECES % 4 == 2,
+              "corpus stage must split evenly over 4 waves");
+// resident workgroups per CU the tile is sized for
+#define KNN_WGS (BM <= 96 ? 3 : 2)
+static_assert(SMEM_BYTES * KNN_WGS <= 160 * 1024, "LDS budget per CU");
+
+namespace knn_mfma_detail {
+
+// Stage-image swizzle (self-inverse). Rows are 64 B = four 16 B slots and
+// a 256 B bank row holds four rows. ds_read_b128 is served in 16-lane
+// groups, each made of the lanes of rows 0-3 and 12-15 of one slot plus
+// the lanes of rows 4-11 of its neighbour slot (g, g^1). With slot ^=
+// 2*(row>>2 & 1) the four rows r, r+4, r+8, r+12 that share a bank-row
+// position (r&3) get the distinct slots {g, g^1^2, g^1, g^2}: 16 distinct
+// 16 B positions per group, conflict-free.
 __device__ __forceinline__ int swz(int b) {
-  return (b & ~127) | ((b & 127) ^ (((b >> 7) & 7) << 4));
+  return b ^ (((b >> 8) & 1) << 5);
 }
+
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    static_for<I + 1, N>(f);
+  }
+}
+
+// LDS byte addresses: addrspace(3) pointer values are byte offsets.
+template <int OFF, class T>
+__device__ __forceinline__ void ds_read128(T& dst, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+}
+template <int OFF>
+__device__ __forceinline__ void ds_write128(unsigned addr, float4v v) {
+  asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF)
+               : "memory");
+}
+// sched_barrier: hipcc otherwise moves register-only MFMA/VALU across an
+// inline-asm wait.
+template <int N>
+__device__ __forceinline__ void wait_lgkm() {
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// One wave-instruction of LDS-DMA: 16 B per lane from gbase + voff to the
+// wave-uniform LDS address lds + lane * 16.
+__device__ __forceinline__ void glds(const char* gbase, unsigned voff,
+                                     char* lds) {
+  __builtin_amdgcn_global_load_lds(
+      (const G_AS unsigned int*)(gbase + voff), (L_AS unsigned int*)lds, 16, 0,
+      0);
+}
+
+}  // namespace knn_mfma_detail
 
 // FILTERED: `allow` is a packed row mask (bit r&31 of word r>>5 set = local
 // row r may be returned); a panel is BM/32 whole words. FILTERED=false
 // never touches `allow`.
 template <bool FILTERED>
-__global__ __launch_bounds__(NTHREADS, 3) void k_knn_mfma(
+__global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
     const unsigned short* __restrict__ db, const unsigned short* __restrict__ qs,
     long long n_panels,  // number of full BM-row panels
-    int d,               // inner dim, % BK == 0
+    int d,               // inner dim, % 64 == 0
     long long row_base, float* __restrict__ cand_score,
     int* __restrict__ cand_idx, const unsigned int* __restrict__ allow) {
+  using namespace knn_mfma_detail;
   static_assert(!FILTERED || BM % 32 == 0,
                 "filtered kNN needs whole mask words per panel");
-  // 44 KB: K-loop uses sA (12 KB) + sB (32 KB); epilogue reuses the same
-  // space as the [256][36] fp32 transposed chunk (36.9 KB).
-  __shared__ __align__(16) char smem[BM * BK * 2 + BN * BK * 2];
-  unsigned short* sA = (unsigned short*)smem;
-  unsigned short* sB = (unsigned short*)(smem + BM * BK * 2);
-  float* sT = (float*)smem;  // epilogue alias [256][36]
+  // One array for all LDS (a second __shared__ object makes hipcc wait
+  // vmcnt(0) ahead of LDS reads): sB[2] at 0, sA[3] behind them.
+  __shared__ __align__(16) char smem[SMEM_BYTES];
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
-  const int wc = tid / WAVE;  // wave col 0..3 (64 cols each)
+  const int wc = __builtin_amdgcn_readfirstlane(tid / WAVE);  // wave 0..3
 
   // per-thread top-K state: this thread owns query column tid.
   float tv[KCAND];
@@ -81,110 +191,175 @@ __global__ __launch_bounds__(NTHREADS, 3) void k_knn_mfma(
 #pragma unroll
   for (int i = 0; i < KCAND; ++i) { tv[i] = -1e30f; ti[i] = -1; }
 
-  const long long d2 = (long long)d * 2;  // row stride in bytes
+  const int d2 = d * 2;       // row stride in bytes
+  const int nstage = d / BK;  // stages per panel, even and >= 2
 
-  for (long long panel = blockIdx.x; panel < n_panels; panel += gridDim.x) {
-    const long long prow = panel * BM;
-
-    // workgroup-uniform mask words of this panel; an all-zero panel is
-    // skipped before any staging (block-uniform, ahead of every barrier)
-    unsigned int aw[(BM + 31) / 32];
+  // first panel of this block that has an allowed row, from p upward
+  auto next_live = [&](long long p) -> long long {
     if constexpr (FILTERED) {
-      unsigned int any = 0;
+      while (p < n_panels) {
+        unsigned int any = 0;
 #pragma unroll
-      for (int h = 0; h < BM / 32; ++h) {
-        aw[h] = allow[(prow >> 5) + h];
-        any |= aw[h];
+        for (int h = 0; h < BM / 32; ++h) any |= allow[((p * BM) >> 5) + h];
+        if (any != 0) break;
+        p += gridDim.x;
       }
-      if (any == 0) continue;
     }
+    return p;
+  };
 
-    float4v acc[MW][4];
-#pragma unroll
-    for (int m = 0; m < MW; ++m)
-#pragma unroll
-      for (int nn = 0; nn < 4; ++nn) acc[m][nn] = {0.f, 0.f, 0.f, 0.f};
+  long long panel = next_live(blockIdx.x);
+  if (panel < n_panels) {  // block-uniform
+    // Staging: lane L of a piece covers LDS bytes x = L*16 (+ piece base, a
+    // multiple of 512 with bit 8 clear), which hold logical bytes swz(x):
+    // row x>>6, slot (L&3) ^ 2*((L>>4)&1). The per-lane source offset is
+    // the same for every piece of either operand.
+    const unsigned voff =
+        (unsigned)((lane >> 2) * d2 +
+                   (((lane & 3) ^ (((lane >> 4) & 1) << 1)) << 4));
+    const char* qbase = (const char*)qs + (long long)(wc * 64) * d2;
 
-    for (int kt = 0; kt < d; kt += BK) {
-      // ---- stage A (96x64 = 12 KB) and B (256x64 = 32 KB) ----
-      // One global_load_lds = one wave writes 64 lanes x 16 B = 1 KB at a
-      // wave-uniform LDS base; the global source address is pre-swizzled
-      // so the LDS image is the swizzled layout.
+    auto issue_b = [&](int s, int boff) {
+      const char* g = qbase + s * (BK * 2);
 #pragma unroll
-      for (int it = 0; it < BM / 32; ++it) {  // A: BM/8 chunks, 4 waves
-        int chunk = wc * (BM / 32) + it;
-        int x = chunk * 1024 + lane * 16;
-        int p = swz(x);
-        const G_AS unsigned int* gp = (const G_AS unsigned int*)(
-            (const char*)db + (prow + (p >> 7)) * d2 + (long long)kt * 2 +
-            (p & 127));
-        L_AS unsigned int* lp = (L_AS unsigned int*)((char*)sA + chunk * 1024);
-        __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+      for (int c = 0; c < NB; ++c)
+        glds(g + (long long)(c * 16) * d2, voff,
+                smem + boff + (wc * NB + c) * 1024);
+    };
+    auto issue_a = [&](long long prow, int s, int aoff) {
+      const char* g = (const char*)db + prow * d2 + s * (BK * 2);
+#pragma unroll
+      for (int c = 0; c < A_FULL; ++c)
+        glds(g + (long long)((wc * A_FULL + c) * 16) * d2, voff,
+                    smem + aoff + (wc * A_FULL + c) * 1024);
+      if constexpr (A_HALF) {
+        // last two pieces as four 8-row halves, one per wave
+        if (lane < 32)
+          glds(g + (long long)(4 * A_FULL * 16 + wc * 8) * d2, voff,
+                      smem + aoff + 4 * A_FULL * 1024 + wc * 512);
       }
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {  // B: 32 chunks, 4 waves x 8
-        int chunk = wc * 8 + it;
-        int x = chunk * 1024 + lane * 16;
-        int p = swz(x);
-        const G_AS unsigned int* gp = (const G_AS unsigned int*)(
-            (const char*)qs + (long long)(p >> 7) * d2 + (long long)kt * 2 +
-            (p & 127));
-        L_AS unsigned int* lp = (L_AS unsigned int*)((char*)sB + chunk * 1024);
-        __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
-      }
-      __syncthreads();
+    };
 
-      // ---- MFMA over the staged tile: 2 k-steps of 32 ----
+    // fragment (row r0 + lane%16, k-slot lane/16) at its swizzled position
+    const unsigned foff = (unsigned)swz((lane & 15) * 64 + (lane >> 4) * 16);
+    const unsigned lds0 = (unsigned)(unsigned long long)(L_AS char*)smem;
+    const unsigned fb = lds0 + wc * (64 * BK * 2) + foff;  // + sB offset
+    const unsigned fa = lds0 + foff;                       // + sA offset
+    // epilogue block [col][16] fp32, 64 B rows, slot ^= (col>>2)&3: the
+    // column owner's float4 reads (one row per lane, same slot) spread a
+    // 16-lane group over 16 distinct 16 B positions.
+    const unsigned ew = lds0 + wc * 4096 + (lane & 15) * 64 +
+                        (((lane >> 4) ^ ((lane >> 2) & 3)) << 4);
+    const unsigned er = tid * 64 + (((tid >> 2) & 3) << 4);  // slot 0
+
+    int b_cur = 0, b_nxt = SB_BYTES;
+    int a_cur = 2 * SB_BYTES, a_nxt = a_cur + SA_BYTES, a_nn = a_nxt + SA_BYTES;
+
+    // prologue: A(0), B(0), A(1); gate the first two
+    issue_a(panel * BM, 0, a_cur);
+    issue_b(0, b_cur);
+    issue_a(panel * BM, 1, a_nxt);
+    wait_vm<NA>();
+    __builtin_amdgcn_s_barrier();
+
+    for (;;) {
+      const long long prow = panel * BM;
+      // the skip decision for the following panel precedes its prefetch
+      const long long nxt = next_live(panel + gridDim.x);
+      const long long prow_pf = (nxt < n_panels ? nxt : panel) * BM;
+
+      unsigned int aw[(BM + 31) / 32];
+      if constexpr (FILTERED) {
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int kb = (ks * 32 + (lane >> 4) * 8) * 2;
-        bf16x8 bfr[4];
+        for (int h = 0; h < BM / 32; ++h) aw[h] = allow[(prow >> 5) + h];
+      }
+
+      float4v acc[MW][4];
 #pragma unroll
-        for (int nn = 0; nn < 4; ++nn) {
-          int c = wc * 64 + nn * 16 + (lane & 15);
-          bfr[nn] = (bf16x8)(*reinterpret_cast<const short8v*>(
-              (const char*)sB + swz(c * 128 + kb)));
+      for (int m = 0; m < MW; ++m)
+#pragma unroll
+        for (int nn = 0; nn < 4; ++nn) acc[m][nn] = {0.f, 0.f, 0.f, 0.f};
+
+      for (int s = 0; s < nstage; ++s) {
+        // ---- prefetch: queries of the next stage, corpus two ahead ----
+        issue_b(s + 1 == nstage ? 0 : s + 1, b_nxt);
+        {
+          const bool wrap = s + 2 >= nstage;
+          issue_a(wrap ? prow_pf : prow, wrap ? s + 2 - nstage : s + 2, a_nn);
         }
-#pragma unroll
-        for (int m = 0; m < MW; ++m) {
-          int r = m * 16 + (lane & 15);
-          bf16x8 af = (bf16x8)(*reinterpret_cast<const short8v*>(
-              (const char*)sA + swz(r * 128 + kb)));
+
+        // ---- fragments of this stage, then MFMA behind counted waits ----
+        // Reads in consumption order: 4 B, the first AH A fragments, then
+        // A fragment m+AH into the registers of fragment m once row group
+        // m has issued its MFMAs (an MFMA reads its A/B operands at issue;
+        // the read returns at least an LDS latency later). LDS returns in
+        // order, so before group m the wave may leave outstanding
+        //   issued(4 + AH + min(m, MW-AH)) - needed(5 + m).
+        constexpr int AH = (MW + 1) / 2;
+        bf16x8 bfr[4], afr[AH];
+        const unsigned rb = fb + b_cur, ra = fa + a_cur;
+        static_for<0, 4>([&](auto nn) {
+          ds_read128<decltype(nn)::value * 1024>(bfr[decltype(nn)::value], rb);
+        });
+        static_for<0, AH>([&](auto m) {
+          ds_read128<decltype(m)::value * 1024>(afr[decltype(m)::value], ra);
+        });
+        __builtin_amdgcn_s_setprio(1);
+        static_for<0, MW>([&](auto mc) {
+          constexpr int m = decltype(mc)::value;
+          constexpr int more = m < MW - AH ? m : MW - AH;
+          wait_lgkm<AH - 1 + more - m>();
 #pragma unroll
           for (int nn = 0; nn < 4; ++nn)
             acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                af, bfr[nn], acc[m][nn], 0, 0, 0);
-        }
-      }
-      __syncthreads();
-    }
+                afr[m % AH], bfr[nn], acc[m][nn], 0, 0, 0);
+          if constexpr (m + AH < MW) {
+            __builtin_amdgcn_sched_barrier(0);
+            ds_read128<(m + AH) * 1024>(afr[m % AH], ra);
+          }
+        });
+        __builtin_amdgcn_s_setprio(0);
 
-    // ---- epilogue: 32-row chunks through the transposed LDS block ----
-#pragma unroll
-    for (int h = 0; h < BM / 32; ++h) {
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        int m = h * 2 + mi;
-#pragma unroll
-        for (int nn = 0; nn < 4; ++nn) {
-          int col = wc * 64 + nn * 16 + (lane & 15);
-          int srow = mi * 16 + (lane >> 4) * 4;
-          *reinterpret_cast<float4v*>(sT + col * 36 + srow) = acc[m][nn];
+        // retire A(g+1) and B(g+1); A(g+2) stays in flight (see header)
+        wait_vm<NA>();
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        {
+          int t = b_cur; b_cur = b_nxt; b_nxt = t;
+          t = a_cur; a_cur = a_nxt; a_nxt = a_nn; a_nn = t;
         }
       }
-      __syncthreads();
-      const long long grow0 = prow + (long long)h * 32;
+
+      // ---- epilogue: 16-row chunks through the transposed block in the
+      // query buffer the last stage read (b_nxt after the swap) ----
+      // the asm stores below read MFMA results: cover the MFMA-write ->
+      // LDS-read wait states the compiler cannot see into the asm for
+      asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+      const unsigned ewb = ew + b_nxt, erb = lds0 + b_nxt;
+      static_for<0, MW>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        static_for<0, 4>([&](auto nn) {
+          ds_write128<decltype(nn)::value * 1024>(ewb,
+                                                  acc[m][decltype(nn)::value]);
+        });
+        wait_lgkm<0>();
+        __builtin_amdgcn_s_barrier();
+        float4v v[4];
+        static_for<0, 4>([&](auto sl) {
+          ds_read128<0>(v[decltype(sl)::value],
+                        erb + (er ^ (unsigned)(decltype(sl)::value << 4)));
+        });
+        wait_lgkm<0>();
+        const long long grow0 = prow + m * 16;
 #pragma unroll
-      for (int j = 0; j < 32; j += 4) {
-        float4v v = *reinterpret_cast<const float4v*>(sT + tid * 36 + j);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float s = v[e];
+        for (int j = 0; j < 16; ++j) {
+          float s = v[j >> 2][j & 3];
           bool ok = s > tv[KCAND - 1];
-          if constexpr (FILTERED) ok = ok && ((aw[h] >> (j + e)) & 1u);
+          if constexpr (FILTERED)
+            ok = ok && ((aw[m >> 1] >> ((m & 1) * 16 + j)) & 1u);
           if (ok) {
             float cs = s;
-            int ci = (int)(grow0 + j + e);
+            int ci = (int)(grow0 + j);
 #pragma unroll
             for (int i = 0; i < KCAND; ++i) {
               bool ins = cs > tv[i];
@@ -195,9 +370,15 @@ __global__ __launch_bounds__(NTHREADS, 3) void k_knn_mfma(
             }
           }
         }
-      }
-      __syncthreads();
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+      });
+
+      if (nxt >= n_panels) break;
+      panel = nxt;
     }
+    // end of stream: retire the unused tail prefetches before the LDS goes
+    wait_vm<0>();
   }
 
   // ---- write candidates ----
@@ -290,6 +471,17 @@ __global__ void k_topk_merge_i32(const float* __restrict__ cand_score,
 // host wrapper: full-panel part of the shard only (n_panels * BM rows).
 // The python side handles the tail rows and q-padding to 256.
 // ---------------------------------------------------------------------------
+template <bool FILTERED>
+static void launch_knn_mfma(int grid, hipStream_t stream, const at::Tensor& db,
+                            const at::Tensor& q, long long n_panels, int d,
+                            long long row_base, at::Tensor& cand_s,
+                            at::Tensor& cand_i, const unsigned int* allow_p) {
+  hipLaunchKernelGGL((k_knn_mfma<FILTERED>), dim3(grid), dim3(NTHREADS),
+                     0, stream, (const unsigned short*)db.data_ptr(),
+                     (const unsigned short*)q.data_ptr(), n_panels, d, row_base,
+                     cand_s.data_ptr<float>(), cand_i.data_ptr<int>(), allow_p);
+}
+
 std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
                                             long long row_base, int k_out,
                                             c10::optional<at::Tensor> allow) {
@@ -303,7 +495,7 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   int d = (int)db.size(1);
   TORCH_CHECK(q.size(0) == BN, "knn_mfma: q must be padded to ", BN, " rows");
   TORCH_CHECK(q.size(1) == d, "dim mismatch");
-  TORCH_CHECK(d % BK == 0, "knn_mfma needs D % 64 == 0");
+  TORCH_CHECK(d % 64 == 0, "knn_mfma needs D % 64 == 0");
   TORCH_CHECK(n % BM == 0, "knn_mfma needs N % ", BM, " == 0 (python pads/tails)");
   TORCH_CHECK(n < (1LL << 31), "shard too large for int32 local rows");
   TORCH_CHECK(k_out >= 1 && k_out <= KCAND);
@@ -311,15 +503,13 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "knn_mfma");
 
   long long n_panels = n / BM;
-  // Enough blocks that each retires quickly (load balance + lets other
-  // streams' kernels co-schedule), few enough that the candidate buffer
-  // and merge stay small. At grid 8192 a 100M-corpus block runs ~6 ms,
-  // which blocks embed-stream GEMMs from co-scheduling; tunable for the
-  // overlap experiment via NORNICDB_KNN_GRID.
-  // multiple of the resident-WG count (3 WGs/CU x 256 CUs = 768) so
-  // every dispatch wave is full: at 8192 the 11th wave ran 512 WGs with
-  // 2/3 of the chip idle (measured ~2-3% of the kernel)
-  int max_grid = 7680;
+  // Persistent-style grid: 1536 = 3 blocks per resident slot at 2
+  // workgroups/CU (and 2 per slot at 3/CU), so every dispatch wave is
+  // full. Each block walks many panels back to back through one stage
+  // stream; its top-k thresholds tighten early and the candidate buffers
+  // and the merge shrink with the grid. Swept at 100M rows (160-row tile):
+  // 7680 61.7 ms, 3072 60.2 ms, 1536 59.4 ms. NORNICDB_KNN_GRID overrides.
+  int max_grid = 1536;
   if (const char* g = getenv("NORNICDB_KNN_GRID")) max_grid = atoi(g);
   int grid = (int)std::min<long long>(n_panels, max_grid);
   auto stream = at::hip::getCurrentHIPStream().stream();
@@ -331,18 +521,12 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   at::Tensor cand_i = at::empty({grid, BN, KCAND}, opts_i32);
 
   if (allow_p == nullptr) {
-    hipLaunchKernelGGL(k_knn_mfma<false>, dim3(grid), dim3(NTHREADS), 0,
-                       stream, (const unsigned short*)db.data_ptr(),
-                       (const unsigned short*)q.data_ptr(), n_panels, d,
-                       row_base, cand_s.data_ptr<float>(),
-                       cand_i.data_ptr<int>(), allow_p);
+    launch_knn_mfma<false>(grid, stream, db, q, n_panels, d, row_base, cand_s,
+                           cand_i, allow_p);
   } else {
 #if KNN_BM % 32 == 0
-    hipLaunchKernelGGL(k_knn_mfma<true>, dim3(grid), dim3(NTHREADS), 0,
-                       stream, (const unsigned short*)db.data_ptr(),
-                       (const unsigned short*)q.data_ptr(), n_panels, d,
-                       row_base, cand_s.data_ptr<float>(),
-                       cand_i.data_ptr<int>(), allow_p);
+    launch_knn_mfma<true>(grid, stream, db, q, n_panels, d, row_base, cand_s,
+                          cand_i, allow_p);
 #else
     TORCH_CHECK(false, "knn_mfma: filtered search needs KNN_BM % 32 == 0");
 #endif
