@@ -7,6 +7,10 @@ void fill_random_unit_(at::Tensor x, long long row_base, long long seed);
 std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
                                             long long row_base, int k_out,
                                             c10::optional<at::Tensor> allow);
+std::tuple<at::Tensor, at::Tensor> ivf_scan(
+    at::Tensor db, at::Tensor q, at::Tensor probes, at::Tensor list_off,
+    at::Tensor list_rows, long long tail_start, long long max_len,
+    long long row_base, int k_out, c10::optional<at::Tensor> allow);
 
 // knn_mfma.hip
 long long knn_bm_value();
@@ -91,6 +95,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "optional packed int32 row mask (bit r&31 of word r>>5)",
         py::arg("db"), py::arg("q"), py::arg("row_base") = 0,
         py::arg("k_out") = 10, py::arg("allow") = c10::nullopt);
+  m.def("ivf_scan", &ivf_scan,
+        "IVF probe-list scan: fused gather + cosine score + top-k (k <= 64) "
+        "over the probed inverted lists and the unclustered tail (bf16 db)",
+        py::arg("db"), py::arg("q"), py::arg("probes"), py::arg("list_off"),
+        py::arg("list_rows"), py::arg("tail_start"), py::arg("max_len"),
+        py::arg("row_base") = 0, py::arg("k_out") = 10,
+        py::arg("allow") = c10::nullopt);
   m.attr("KNN_BM") = KNN_BM_VALUE;
   m.def("knn_mfma", &knn_mfma,
         "Fused MFMA cosine score + top-k, 256-query batches (bf16 db)",

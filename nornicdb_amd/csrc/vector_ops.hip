@@ -1,6 +1,6 @@
 // Tier-1 vector kernels for NornicDB-AMD: L2 normalize, synthetic corpus
 // generation, fused cosine-score + top-k (GEMV path for small query batches),
-// and the cross-block top-k merge.
+// the cross-block top-k merge, and the IVF probe-list scan.
 //
 // Re-designs (not ports of) the reference's CUDA kernels
 // (reference: pkg/gpu/cuda/cuda_kernels.cu:185-460 — 1-thread-per-vector
@@ -251,8 +251,11 @@ DEV_INLINE float mono_f32(unsigned int m) {
   return __uint_as_float(u);
 }
 
+// Always launched with 256 threads; the bound lets K=64 keep its lists in
+// registers (192 of them) instead of spilling at the default 128-VGPR cap.
 template <int K>
-__global__ void k_topk_merge(const float* __restrict__ cand_score,
+__global__ void __launch_bounds__(256)
+k_topk_merge(const float* __restrict__ cand_score,
                              const long long* __restrict__ cand_idx,
                              long long w, int q_count, int k_out,
                              float* __restrict__ out_score,
@@ -324,6 +327,176 @@ __global__ void k_topk_merge(const float* __restrict__ cand_score,
     }
     __syncthreads();
     // re-broadcast head increment handled per-thread (winner only)
+  }
+}
+
+// ---------------------------------------------------------------------------
+// IVF probe-list scan: fused gather + cosine-score + per-block top-K.
+//
+// The corpus stays in slot order; an inverted list is a CSR slice of slot
+// numbers (list_rows[list_off[c] .. list_off[c+1])). One 256-thread block
+// serves one (query, probe, split) triple: it stages its query in LDS and
+// its 16 lane-groups stride through the list's entries, each group scoring
+// one gathered row per step with the gemv kernel's dot product (a row is
+// d*2 contiguous bytes, so every 16-lane load is still fully coalesced).
+// Probe slot n_probe is the tail pseudo-list: rows [tail_start, n) with
+// the identity mapping, scanned by every query.
+//
+// After the butterfly every lane of a group holds the same score, so all
+// 16 lanes run the same register insert and the block ends with 16 sorted
+// K-lists. They go to LDS and each of the 16*K entries finds its rank in
+// the union by a binary search in every list (ties broken by position, so
+// ranks are a permutation); ranks < K are written out. That leaves ONE
+// candidate list per block for k_topk_merge, in its [W][Q][K] layout with
+// W = p_eff * split.
+//
+// A probe outside [0, n_lists), or equal to an earlier probe of the same
+// query, scans nothing. List entries are accepted only when they name a
+// row below tail_start, so no row is scored twice or read out of bounds.
+// FILTERED tests the allow bit before the row is loaded (allow_mask.h).
+// ---------------------------------------------------------------------------
+template <int K, bool FILTERED>
+__global__ void __launch_bounds__(256)
+k_ivf_scan_bf16(const unsigned short* __restrict__ db,
+                const unsigned short* __restrict__ qs,
+                const int* __restrict__ probes,
+                const int* __restrict__ list_off,
+                const int* __restrict__ list_rows,
+                int n_lists, long long n_entries, int n_probe, int p_eff,
+                int split, int tail_start, int n, int d, int q_count,
+                long long row_base,
+                float* __restrict__ cand_score,
+                long long* __restrict__ cand_idx,
+                const unsigned int* __restrict__ allow) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  unsigned short* s_q = reinterpret_cast<unsigned short*>(s_raw);  // [d]
+  float* s_ls = reinterpret_cast<float*>(s_raw + (size_t)d * 2);   // [16][K]
+  int* s_li = reinterpret_cast<int*>(s_ls + 16 * K);               // [16][K]
+
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int grp = lane >> 4;
+  const int gl = lane & 15;
+  const int wid = threadIdx.x / WAVE;
+  const int g16 = wid * 4 + grp;    // lane-group within the block, 0..15
+
+  const int sp = blockIdx.x % split;
+  const int p = (blockIdx.x / split) % p_eff;
+  const int q = blockIdx.x / (split * p_eff);
+
+  for (int i = threadIdx.x * 8; i < d; i += blockDim.x * 8) {
+    *reinterpret_cast<short8v*>(s_q + i) =
+        *reinterpret_cast<const short8v*>(qs + (long long)q * d + i);
+  }
+
+  // entries [begin, end) of this block's list; block-uniform
+  const bool tail = (p == n_probe);
+  long long begin = 0, end = 0;
+  if (tail) {
+    begin = tail_start;
+    end = n;
+  } else {
+    const int* pq = probes + (long long)q * n_probe;
+    const int c = pq[p];
+    if (c >= 0 && c < n_lists) {
+      bool dup = false;
+      for (int j = 0; j < p; ++j) dup |= (pq[j] == c);
+      if (!dup) {
+        begin = max(list_off[c], 0);
+        end = min((long long)list_off[c + 1], n_entries);
+      }
+    }
+  }
+  const unsigned int row_limit = tail ? (unsigned int)n : (unsigned int)tail_start;
+  __syncthreads();
+
+  float tv[K];
+  int ti[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) { tv[i] = -1e30f; ti[i] = -1; }
+
+  const int nj = d / 128;
+  const long long stride = (long long)split * 16;
+  long long e = begin + sp * 16 + g16;
+  int row = -1;
+  if (e < end) row = tail ? (int)e : list_rows[e];
+  while (e < end) {
+    // next entry's slot number is fetched before this row is scored
+    const long long e_next = e + stride;
+    int row_next = -1;
+    if (e_next < end) row_next = tail ? (int)e_next : list_rows[e_next];
+
+    bool ok = (unsigned int)row < row_limit;
+    if constexpr (FILTERED) {
+      if (ok) ok = (allow[row >> 5] >> (row & 31)) & 1u;
+    }
+    if (ok) {
+      const unsigned short* rp = db + (long long)row * d + gl * 8;
+      float acc = 0.0f;
+#pragma unroll 8
+      for (int jj = 0; jj < nj; ++jj) {
+        short8v v = *reinterpret_cast<const short8v*>(rp + jj * 128);
+        short8v qv = *reinterpret_cast<const short8v*>(s_q + jj * 128 + gl * 8);
+        const bf16x2v* xa = reinterpret_cast<const bf16x2v*>(&v);
+        const bf16x2v* qa = reinterpret_cast<const bf16x2v*>(&qv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc = __builtin_amdgcn_fdot2_f32_bf16(xa[j], qa[j], acc, false);
+      }
+#pragma unroll
+      for (int off = 1; off < 16; off <<= 1)
+        acc += __shfl_xor(acc, off, WAVE);
+      // same score in all 16 lanes of the group: uniform insert
+      if (acc > tv[K - 1]) {
+        float cs = acc; int ci = row;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+          bool ins = cs > tv[i];
+          float ts = tv[i]; int tj = ti[i];
+          tv[i] = ins ? cs : tv[i];
+          ti[i] = ins ? ci : ti[i];
+          cs = ins ? ts : cs; ci = ins ? tj : ci;
+        }
+      }
+    }
+    e = e_next;
+    row = row_next;
+  }
+
+  if (gl == 0) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      s_ls[g16 * K + i] = tv[i];
+      s_li[g16 * K + i] = ti[i];
+    }
+  }
+  __syncthreads();
+
+  // rank of every entry in the union of the 16 sorted lists
+  const long long out_base =
+      (((long long)p * split + sp) * q_count + q) * K;
+  for (int x = threadIdx.x; x < 16 * K; x += blockDim.x) {
+    const float xs = s_ls[x];
+    int rank = 0;
+#pragma unroll 4
+    for (int l = 0; l < 16; ++l) {
+      const float* ls = s_ls + l * K;
+      const int pos0 = l * K;
+      int lo = 0;
+#pragma unroll
+      for (int step = K / 2; step >= 1; step >>= 1) {
+        const int j = lo + step - 1;
+        const float a = ls[j];
+        lo += (a > xs || (a == xs && pos0 + j < x)) ? step : 0;
+      }
+      const float a = ls[lo];
+      lo += (a > xs || (a == xs && pos0 + lo < x)) ? 1 : 0;
+      rank += lo;
+    }
+    if (rank < K) {
+      const int r = s_li[x];
+      cand_score[out_base + rank] = xs;
+      cand_idx[out_base + rank] = r < 0 ? -1LL : row_base + (long long)r;
+    }
   }
 }
 
@@ -422,5 +595,120 @@ std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
                      reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()), waves, qc, k_out,
                      out_s.data_ptr<float>(), reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()));
   HIP_CHECK_LAST();
+  return {out_s, out_i};
+}
+
+// ---------------------------------------------------------------------------
+// IVF scan + merge. probes [Q][P] int32 (any value outside [0, C) skips);
+// list_off [C+1] / list_rows [M] int32 CSR of slot numbers below tail_start;
+// rows [tail_start, N) are scanned by every query. max_len is the longest
+// list, recorded when the lists were built (no device sync per search).
+// ---------------------------------------------------------------------------
+template <int K>
+static void ivf_scan_launch(const at::Tensor& db, const at::Tensor& q,
+                            const at::Tensor& probes,
+                            const at::Tensor& list_off,
+                            const at::Tensor& list_rows, int p_eff, int split,
+                            int tail_start, long long row_base, int k_out,
+                            const unsigned int* allow_p, at::Tensor& out_s,
+                            at::Tensor& out_i) {
+  const int n = (int)db.size(0);
+  const int d = (int)db.size(1);
+  const int qc = (int)q.size(0);
+  const int n_probe = (int)probes.size(1);
+  const long long w = (long long)p_eff * split;
+  at::Tensor cand_s = at::empty({w, qc, K}, out_s.options());
+  at::Tensor cand_i = at::empty({w, qc, K}, out_i.options());
+  const size_t lds = (size_t)d * 2 + (size_t)16 * K * 8;
+  TORCH_CHECK(lds <= 64 * 1024, "ivf_scan: D too large for the LDS query tile");
+  auto launch = allow_p ? k_ivf_scan_bf16<K, true> : k_ivf_scan_bf16<K, false>;
+  hipLaunchKernelGGL(launch, dim3((unsigned)(w * qc)), dim3(256), lds,
+                     cur_stream(), (const unsigned short*)db.data_ptr(),
+                     (const unsigned short*)q.data_ptr(),
+                     probes.data_ptr<int>(), list_off.data_ptr<int>(),
+                     list_rows.data_ptr<int>(), (int)list_off.numel() - 1,
+                     (long long)list_rows.numel(), n_probe, p_eff, split,
+                     tail_start, n, d, qc, row_base,
+                     cand_s.data_ptr<float>(),
+                     reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()),
+                     allow_p);
+  HIP_CHECK_LAST();
+  hipLaunchKernelGGL((k_topk_merge<K>), dim3(qc), dim3(256), 0, cur_stream(),
+                     cand_s.data_ptr<float>(),
+                     reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()),
+                     w, qc, k_out, out_s.data_ptr<float>(),
+                     reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()));
+  HIP_CHECK_LAST();
+}
+
+std::tuple<at::Tensor, at::Tensor> ivf_scan(
+    at::Tensor db, at::Tensor q, at::Tensor probes, at::Tensor list_off,
+    at::Tensor list_rows, long long tail_start, long long max_len,
+    long long row_base, int k_out, c10::optional<at::Tensor> allow) {
+  TORCH_CHECK(db.is_cuda() && db.dim() == 2 && db.is_contiguous() &&
+                  db.scalar_type() == at::kBFloat16,
+              "ivf_scan: db must be contiguous 2D bf16 CUDA");
+  TORCH_CHECK(q.is_cuda() && q.dim() == 2 && q.is_contiguous() &&
+                  q.scalar_type() == at::kBFloat16,
+              "ivf_scan: q must be contiguous 2D bf16 CUDA");
+  for (const at::Tensor* t : {&probes, &list_off, &list_rows})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == at::kInt,
+                "ivf_scan: probes, list_off and list_rows must be contiguous "
+                "int32 CUDA tensors");
+  TORCH_CHECK(q.device() == db.device() && probes.device() == db.device() &&
+                  list_off.device() == db.device() &&
+                  list_rows.device() == db.device(),
+              "ivf_scan: all tensors must be on db's device");
+  const long long n = db.size(0);
+  const int d = (int)db.size(1);
+  const long long qc = q.size(0);
+  TORCH_CHECK(q.size(1) == d, "ivf_scan: dim mismatch");
+  TORCH_CHECK(d % 128 == 0, "ivf_scan needs D % 128 == 0");
+  TORCH_CHECK(n <= 0x7fffffffLL, "ivf_scan: int32 slot numbers, N < 2^31");
+  TORCH_CHECK(qc >= 1, "ivf_scan: need at least one query");
+  TORCH_CHECK(probes.dim() == 2 && probes.size(0) == qc,
+              "ivf_scan: probes must be [Q, P]");
+  TORCH_CHECK(list_off.dim() == 1 && list_off.numel() >= 1 &&
+                  list_rows.dim() == 1,
+              "ivf_scan: list_off must be [C+1] and list_rows [M]");
+  TORCH_CHECK(tail_start >= 0 && tail_start <= n,
+              "ivf_scan: tail_start must be in [0, N]");
+  TORCH_CHECK(max_len >= 0, "ivf_scan: max_len must be >= 0");
+  TORCH_CHECK(k_out >= 1 && k_out <= 64, "ivf_scan: k_out must be in 1..64");
+  const unsigned int* allow_p = nullptr;
+  if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "ivf_scan");
+
+  auto opts_f = db.options().dtype(at::kFloat);
+  auto opts_i = db.options().dtype(at::kLong);
+  const long long n_probe = probes.size(1);
+  const long long tail_len = n - tail_start;
+  const long long p_eff = n_probe + (tail_len > 0 ? 1 : 0);
+  if (p_eff == 0)
+    return {at::full({qc, (long long)k_out}, -1e30f, opts_f),
+            at::full({qc, (long long)k_out}, -1LL, opts_i)};
+
+  // ~4 blocks per CU over the whole grid, but every split of the longest
+  // list keeps at least block_rows rows: each block adds one candidate
+  // list to the merge, which costs more than the rows it would take over
+  // (4M x 1024, Q=1, nprobe=8: 74 us at 16 rows, 42 us at 128, 49 at 256)
+  int block_rows = 128;
+  if (const char* g = getenv("NORNICDB_IVF_BLOCK_ROWS"))
+    block_rows = std::max(atoi(g), 1);
+  const long long longest = std::max<long long>(std::max(max_len, tail_len), 1);
+  long long split = std::max<long long>(1024 / (qc * p_eff), 1);
+  split = std::min(split, (longest + block_rows - 1) / block_rows);
+  TORCH_CHECK(qc * p_eff * split <= 0x7fffffffLL, "ivf_scan: grid too large");
+
+  at::Tensor out_s = at::empty({qc, (long long)k_out}, opts_f);
+  at::Tensor out_i = at::empty({qc, (long long)k_out}, opts_i);
+  if (k_out <= 16)
+    ivf_scan_launch<16>(db, q, probes, list_off, list_rows, (int)p_eff,
+                        (int)split, (int)tail_start, row_base, k_out, allow_p,
+                        out_s, out_i);
+  else
+    ivf_scan_launch<64>(db, q, probes, list_off, list_rows, (int)p_eff,
+                        (int)split, (int)tail_start, row_base, k_out, allow_p,
+                        out_s, out_i);
   return {out_s, out_i};
 }

@@ -41,3 +41,6 @@ from .vector import l2_normalize_, fill_random_unit_  # noqa: E402,F401
 from .knn import (  # noqa: E402,F401
     knn_search, knn_search_exact, pack_allow_mask, unpack_allow_mask,
 )
+from .ivf import (  # noqa: E402,F401
+    IVFLists, ivf_build_lists, ivf_route, ivf_search, ivf_search_exact,
+)

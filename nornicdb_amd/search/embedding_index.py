@@ -53,6 +53,9 @@ class EmbeddingIndex:
         self._live = np.zeros(capacity, dtype=bool)
         self._live_dirty = True
         self._live_words: Optional[torch.Tensor] = None
+        # called with the slot when add()/add_batch() overwrite a stored
+        # vector in place (IVFIndex counts such slots as stale)
+        self._overwrite_hooks: List = []
 
     def __len__(self):
         return self._n - len(self._dead)
@@ -97,6 +100,8 @@ class EmbeddingIndex:
                     self._scales[slot] = sc[0]
                 self._dead.discard(slot)
                 self._set_live(slot, True)
+                for hook in self._overwrite_hooks:
+                    hook(slot)
                 return
             self._grow(self._n + 1)
             self._buf[self._n] = v[0]
@@ -120,6 +125,8 @@ class EmbeddingIndex:
                         self._scales[slot] = sc[i]
                     self._dead.discard(slot)
                     self._set_live(slot, True)
+                    for hook in self._overwrite_hooks:
+                        hook(slot)
                 else:
                     self._buf[self._n] = m[i]
                     if sc is not None:

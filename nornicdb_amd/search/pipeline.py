@@ -3,7 +3,9 @@
 Parity: reference pkg/search/vector_pipeline.go — brute force below 5K
 vectors (:22-24), HNSW in the mid range, k-means cluster routing above
 100K (kmeans_candidate_gen.go), candidate set max(20k, 200) capped at
-5000 (:26-31), exact re-scoring on GPU (:236 GPUExactScorer).
+5000 (:26-31), exact re-scoring on GPU (:236 GPUExactScorer). An opt-in
+IVFIndex (search/ivf.py) replaces the host-side cluster routing with
+inverted lists scanned on the device.
 """
 
 from __future__ import annotations
@@ -12,6 +14,7 @@ from typing import Iterable, List, Optional, Tuple
 
 from .embedding_index import EmbeddingIndex
 from .hnsw import HNSWIndex
+from .ivf import IVFIndex
 from .kmeans import ClusterIndex
 
 BRUTE_MAX = 5_000
@@ -24,23 +27,35 @@ def candidate_count(k: int) -> int:
 
 class VectorSearchPipeline:
     def __init__(self, emb: EmbeddingIndex, hnsw: Optional[HNSWIndex] = None,
-                 clusters: Optional[ClusterIndex] = None):
+                 clusters: Optional[ClusterIndex] = None,
+                 ivf: Optional[IVFIndex] = None):
         self.emb = emb
         self.hnsw = hnsw
         self.clusters = clusters
+        self.ivf = ivf
 
     def search(self, query, k: int,
-               allow_ids: Optional[Iterable[str]] = None
+               allow_ids: Optional[Iterable[str]] = None,
+               nprobe: Optional[int] = None
                ) -> List[Tuple[str, float]]:
         """allow_ids restricts hits to those ids: the brute-force branches
         filter inside the kNN kernel; the HNSW and cluster branches
         intersect their candidates with it and fall back to the filtered
-        brute-force search when fewer than k survive."""
+        brute-force search when fewer than k survive.
+
+        With a built IVFIndex, corpora above KMEANS_MIN (or any call that
+        passes nprobe) are served by the device-resident IVF search, which
+        applies allow_ids inside its kernel. Without one, nprobe is
+        ignored."""
         n = len(self.emb)
         if n == 0:
             return []
         if allow_ids is not None and not isinstance(allow_ids, (set, frozenset)):
             allow_ids = set(allow_ids)
+        if self.ivf is not None and self.ivf.built and (
+                n > KMEANS_MIN or nprobe is not None):
+            return self.ivf.search(query, k, nprobe=nprobe,
+                                   allow_ids=allow_ids)
         # brute force: small corpora, or GPU path (fused kernel IS the fast path)
         if n <= BRUTE_MAX or (self.emb.device.type == "cuda"
                               and (self.clusters is None or self.clusters.k == 0)):

@@ -19,6 +19,7 @@ from .bm25 import FulltextIndex
 from .embedding_index import EmbeddingIndex
 from .fusion import mmr_diversify, rrf_fuse
 from .hnsw import HNSWIndex
+from .ivf import IVFIndex
 from .kmeans import ClusterIndex, optimal_k
 from .pipeline import KMEANS_MIN, VectorSearchPipeline
 
@@ -45,7 +46,8 @@ class SearchResult:
 class SearchService:
     def __init__(self, engine: Engine, dims: int = 1024,
                  device: Optional[str] = None, use_hnsw: bool = True,
-                 embedder=None, quant: Optional[str] = None):
+                 embedder=None, quant: Optional[str] = None,
+                 ivf: bool = False):
         self.engine = engine
         self.dims = dims
         self.embedder = embedder
@@ -60,7 +62,14 @@ class SearchService:
         self.emb = EmbeddingIndex(dims, device=device, quant=quant)
         self.hnsw = HNSWIndex(dims) if use_hnsw else None
         self.clusters = ClusterIndex()
-        self.pipeline = VectorSearchPipeline(self.emb, self.hnsw, self.clusters)
+        # opt-in device-resident IVF search (ivf=True or
+        # NORNICDB_SEARCH_IVF=1): recluster() also freezes the clusters as
+        # inverted lists on the device, and the pipeline routes large
+        # corpora (or any query that passes nprobe) to them
+        ivf = ivf or _os.environ.get("NORNICDB_SEARCH_IVF") == "1"
+        self.ivf = IVFIndex(self.emb) if ivf else None
+        self.pipeline = VectorSearchPipeline(self.emb, self.hnsw,
+                                             self.clusters, ivf=self.ivf)
         # label -> ids of nodes with an embedding; the vector path turns a
         # label predicate into the kNN allow-mask instead of over-fetching
         self._label_ids: Dict[str, set] = {}
@@ -141,12 +150,17 @@ class SearchService:
             slot_ids = [i for i in self.emb._ids if i in self.emb._id2slot]
             self.clusters.cluster(slot_ids, mat[: len(self.emb._ids)],
                                   k=k or optimal_k(len(slot_ids)))
+            if self.ivf is not None:
+                self.ivf.build(n_lists=k)
 
     # ---- queries ----
     def vector_search(self, query_vec, k: int = 10,
-                      labels: Sequence[str] = None) -> List[SearchResult]:
+                      labels: Sequence[str] = None,
+                      nprobe: Optional[int] = None) -> List[SearchResult]:
+        """nprobe: IVF lists to probe; only read when IVF is enabled."""
         hits = self.pipeline.search(np.asarray(query_vec, np.float32), k,
-                                    allow_ids=self._allow_ids(labels))
+                                    allow_ids=self._allow_ids(labels),
+                                    nprobe=nprobe)
         return self._materialize(hits, k, labels, source="vector")
 
     def text_search(self, query: str, k: int = 10,
@@ -156,8 +170,10 @@ class SearchService:
 
     def search(self, query: str = None, query_vec=None, k: int = 10,
                labels: Sequence[str] = None, mmr: bool = False,
-               mmr_lambda: float = 0.7) -> List[SearchResult]:
-        """Hybrid search: BM25 + vector fused with RRF; optional MMR."""
+               mmr_lambda: float = 0.7,
+               nprobe: Optional[int] = None) -> List[SearchResult]:
+        """Hybrid search: BM25 + vector fused with RRF; optional MMR.
+        nprobe: IVF lists to probe; only read when IVF is enabled."""
         if query_vec is None and query and self.embedder is not None:
             query_vec = self.embedder.embed_query(query)
         rankings = []
@@ -166,7 +182,7 @@ class SearchService:
         if query_vec is not None and len(self.emb) > 0:
             rankings.append(self.pipeline.search(
                 np.asarray(query_vec, np.float32), max(k * 4, 40),
-                allow_ids=self._allow_ids(labels)))
+                allow_ids=self._allow_ids(labels), nprobe=nprobe))
         if not rankings:
             return []
         if len(rankings) == 1:

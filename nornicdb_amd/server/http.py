@@ -70,6 +70,7 @@ class SearchRequest(BaseModel):
     limit: int = 10
     labels: Optional[List[str]] = None
     mmr: bool = False
+    nprobe: Optional[int] = None   # IVF lists to probe (needs search IVF on)
 
 
 class LoginRequest(BaseModel):
@@ -635,7 +636,8 @@ def create_app(mgr: DatabaseManager, auth=None, version: str = "0.1.0") -> FastA
         d = mgr.get(db)
         qv = d.embedder.embed_query(req.query)
         res = d.search.search(query=req.query, query_vec=qv, k=req.limit,
-                              labels=req.labels, mmr=req.mmr)
+                              labels=req.labels, mmr=req.mmr,
+                              nprobe=req.nprobe)
         return {"results": [{"id": r.id, "score": r.score,
                              "node": _jsonable(r.node)} for r in res]}
 

@@ -48,6 +48,13 @@ def main():
     dt = t(lambda: ops.knn_search(x, q256, 10))
     print(f"knn fused-MFMA Q=256: {dt*1e3:.2f} ms  {gb/dt:.0f} GB/s(db)  {256/dt:.0f} qps")
 
+    # IVF scan over random lists (timing only; scripts/ivf_bench.py clusters)
+    lists = ops.ivf_build_lists(torch.randint(0, 1414, (n,), device=dev), 1414, n, x[:1414].float())
+    for qq in (q1, q16):
+        pr = ops.ivf_route(lists, qq, 8)
+        dt = t(lambda: ops.ivf_search(x, qq, 10, lists, pr, n), iters=100)
+        print(f"ivf_search Q={qq.shape[0]} nprobe=8 C=1414: {dt*1e3:.3f} ms  {qq.shape[0]/dt:.0f} qps")
+
     gb4 = n * d * 2 / 1e9
     print(f"  (mfma fused path active for Q=256: reads {gb4:.1f} GB once)")
 
