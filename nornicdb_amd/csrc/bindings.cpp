@@ -11,6 +11,15 @@ std::tuple<at::Tensor, at::Tensor> ivf_scan(
     at::Tensor db, at::Tensor q, at::Tensor probes, at::Tensor list_off,
     at::Tensor list_rows, long long tail_start, long long max_len,
     long long row_base, int k_out, c10::optional<at::Tensor> allow);
+std::tuple<at::Tensor, at::Tensor> ivf_scan_i8(
+    at::Tensor db, at::Tensor sa, at::Tensor q, at::Tensor sq,
+    at::Tensor probes, at::Tensor list_off, at::Tensor list_rows,
+    long long tail_start, long long max_len, long long row_base, int k_out,
+    c10::optional<at::Tensor> allow);
+std::tuple<at::Tensor, at::Tensor> ivf_scan_fp8(
+    at::Tensor db, at::Tensor q, at::Tensor probes, at::Tensor list_off,
+    at::Tensor list_rows, long long tail_start, long long max_len,
+    long long row_base, int k_out, c10::optional<at::Tensor> allow);
 
 // knn_mfma.hip
 long long knn_bm_value();
@@ -98,6 +107,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ivf_scan", &ivf_scan,
         "IVF probe-list scan: fused gather + cosine score + top-k (k <= 64) "
         "over the probed inverted lists and the unclustered tail (bf16 db)",
+        py::arg("db"), py::arg("q"), py::arg("probes"), py::arg("list_off"),
+        py::arg("list_rows"), py::arg("tail_start"), py::arg("max_len"),
+        py::arg("row_base") = 0, py::arg("k_out") = 10,
+        py::arg("allow") = c10::nullopt);
+  m.def("ivf_scan_i8", &ivf_scan_i8,
+        "IVF probe-list scan over a symmetric int8 corpus with per-row "
+        "scales (score = i32 dot * sa[row] * sq[query]); q is the int8 "
+        "query, sq its scales",
+        py::arg("db"), py::arg("sa"), py::arg("q"), py::arg("sq"),
+        py::arg("probes"), py::arg("list_off"), py::arg("list_rows"),
+        py::arg("tail_start"), py::arg("max_len"), py::arg("row_base") = 0,
+        py::arg("k_out") = 10, py::arg("allow") = c10::nullopt);
+  m.def("ivf_scan_fp8", &ivf_scan_fp8,
+        "IVF probe-list scan over an FP8 e4m3fn corpus (uint8 carrier for "
+        "db and q), fp32 accumulation",
         py::arg("db"), py::arg("q"), py::arg("probes"), py::arg("list_off"),
         py::arg("list_rows"), py::arg("tail_start"), py::arg("max_len"),
         py::arg("row_base") = 0, py::arg("k_out") = 10,

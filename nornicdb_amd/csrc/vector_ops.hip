@@ -500,6 +500,200 @@ k_ivf_scan_bf16(const unsigned short* __restrict__ db,
   }
 }
 
+// ---------------------------------------------------------------------------
+// The same scan over a 1-byte-per-element corpus: symmetric int8 with
+// per-row scales, or OCP e4m3 fp8. Block contract, list walk, insert and
+// epilogue are those of k_ivf_scan_bf16 (its text is repeated, not shared,
+// so that kernel's register allocation stays as measured); only the row
+// score differs. A row is d contiguous bytes: per 128 elements each of a
+// group's 16 lanes loads 8 of them, against 8 query bytes from LDS.
+//
+// int8: the query arrives quantised (int8 [Q][d] and its scale sq[q]);
+//   v_dot4 accumulates into an int32 that the butterfly reduces exactly,
+//   score = float(dot) * sa[row] * sq[q] as in k_knn_i8. sa is indexed by
+//   slot number and loaded ahead of the row's data.
+// fp8: row and query bytes are converted in pairs (v_cvt_pk_f32_fp8, exact)
+//   and accumulated in fp32.
+// ---------------------------------------------------------------------------
+enum { IVF_FMT_I8 = 0, IVF_FMT_FP8 = 1 };
+typedef unsigned int uint2v __attribute__((ext_vector_type(2)));   // 8B
+
+template <int K, bool FILTERED, int FMT>
+__global__ void __launch_bounds__(256)
+k_ivf_scan_q8(const unsigned char* __restrict__ db,
+              const unsigned char* __restrict__ qs,
+              const float* __restrict__ sa,    // [n], int8 only
+              const float* __restrict__ sq,    // [q_count], int8 only
+              const int* __restrict__ probes,
+              const int* __restrict__ list_off,
+              const int* __restrict__ list_rows,
+              int n_lists, long long n_entries, int n_probe, int p_eff,
+              int split, int tail_start, int n, int d, int q_count,
+              long long row_base,
+              float* __restrict__ cand_score,
+              long long* __restrict__ cand_idx,
+              const unsigned int* __restrict__ allow) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  unsigned char* s_q = s_raw;                                      // [d]
+  float* s_ls = reinterpret_cast<float*>(s_raw + (size_t)d);       // [16][K]
+  int* s_li = reinterpret_cast<int*>(s_ls + 16 * K);               // [16][K]
+
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int grp = lane >> 4;
+  const int gl = lane & 15;
+  const int wid = threadIdx.x / WAVE;
+  const int g16 = wid * 4 + grp;    // lane-group within the block, 0..15
+
+  const int sp = blockIdx.x % split;
+  const int p = (blockIdx.x / split) % p_eff;
+  const int q = blockIdx.x / (split * p_eff);
+
+  for (int i = threadIdx.x * 8; i < d; i += blockDim.x * 8) {
+    *reinterpret_cast<uint2v*>(s_q + i) =
+        *reinterpret_cast<const uint2v*>(qs + (long long)q * d + i);
+  }
+  float q_scale = 1.0f;
+  if constexpr (FMT == IVF_FMT_I8) q_scale = sq[q];
+
+  // entries [begin, end) of this block's list; block-uniform
+  const bool tail = (p == n_probe);
+  long long begin = 0, end = 0;
+  if (tail) {
+    begin = tail_start;
+    end = n;
+  } else {
+    const int* pq = probes + (long long)q * n_probe;
+    const int c = pq[p];
+    if (c >= 0 && c < n_lists) {
+      bool dup = false;
+      for (int j = 0; j < p; ++j) dup |= (pq[j] == c);
+      if (!dup) {
+        begin = max(list_off[c], 0);
+        end = min((long long)list_off[c + 1], n_entries);
+      }
+    }
+  }
+  const unsigned int row_limit = tail ? (unsigned int)n : (unsigned int)tail_start;
+  __syncthreads();
+
+  float tv[K];
+  int ti[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) { tv[i] = -1e30f; ti[i] = -1; }
+
+  const int nj = d / 128;
+  const long long stride = (long long)split * 16;
+  long long e = begin + sp * 16 + g16;
+  int row = -1;
+  if (e < end) row = tail ? (int)e : list_rows[e];
+  while (e < end) {
+    // next entry's slot number is fetched before this row is scored
+    const long long e_next = e + stride;
+    int row_next = -1;
+    if (e_next < end) row_next = tail ? (int)e_next : list_rows[e_next];
+
+    bool ok = (unsigned int)row < row_limit;
+    if constexpr (FILTERED) {
+      if (ok) ok = (allow[row >> 5] >> (row & 31)) & 1u;
+    }
+    if (ok) {
+      const unsigned char* rp = db + (long long)row * d + gl * 8;
+      const unsigned char* qp = s_q + gl * 8;
+      float score;
+      if constexpr (FMT == IVF_FMT_I8) {
+        // its own cache line per row: in flight with the row's data
+        const float row_scale = sa[row];
+        int acc = 0;
+#pragma unroll 8
+        for (int jj = 0; jj < nj; ++jj) {
+          uint2v v = *reinterpret_cast<const uint2v*>(rp + jj * 128);
+          uint2v qv = *reinterpret_cast<const uint2v*>(qp + jj * 128);
+          acc = __builtin_amdgcn_sdot4((int)v.x, (int)qv.x, acc, false);
+          acc = __builtin_amdgcn_sdot4((int)v.y, (int)qv.y, acc, false);
+        }
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1)
+          acc += __shfl_xor(acc, off, WAVE);
+        score = (float)acc * row_scale * q_scale;
+      } else {
+        float acc = 0.0f;
+#pragma unroll 8
+        for (int jj = 0; jj < nj; ++jj) {
+          uint2v v = *reinterpret_cast<const uint2v*>(rp + jj * 128);
+          uint2v qv = *reinterpret_cast<const uint2v*>(qp + jj * 128);
+          const unsigned int xw[2] = {v.x, v.y}, qw[2] = {qv.x, qv.y};
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            float2v x0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)xw[j], false);
+            float2v x1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)xw[j], true);
+            float2v q0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)qw[j], false);
+            float2v q1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)qw[j], true);
+            acc = fmaf(x0.x, q0.x, acc);
+            acc = fmaf(x0.y, q0.y, acc);
+            acc = fmaf(x1.x, q1.x, acc);
+            acc = fmaf(x1.y, q1.y, acc);
+          }
+        }
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1)
+          acc += __shfl_xor(acc, off, WAVE);
+        score = acc;
+      }
+      // same score in all 16 lanes of the group: uniform insert
+      if (score > tv[K - 1]) {
+        float cs = score; int ci = row;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+          bool ins = cs > tv[i];
+          float ts = tv[i]; int tj = ti[i];
+          tv[i] = ins ? cs : tv[i];
+          ti[i] = ins ? ci : ti[i];
+          cs = ins ? ts : cs; ci = ins ? tj : ci;
+        }
+      }
+    }
+    e = e_next;
+    row = row_next;
+  }
+
+  if (gl == 0) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      s_ls[g16 * K + i] = tv[i];
+      s_li[g16 * K + i] = ti[i];
+    }
+  }
+  __syncthreads();
+
+  // rank of every entry in the union of the 16 sorted lists
+  const long long out_base =
+      (((long long)p * split + sp) * q_count + q) * K;
+  for (int x = threadIdx.x; x < 16 * K; x += blockDim.x) {
+    const float xs = s_ls[x];
+    int rank = 0;
+#pragma unroll 4
+    for (int l = 0; l < 16; ++l) {
+      const float* ls = s_ls + l * K;
+      const int pos0 = l * K;
+      int lo = 0;
+#pragma unroll
+      for (int step = K / 2; step >= 1; step >>= 1) {
+        const int j = lo + step - 1;
+        const float a = ls[j];
+        lo += (a > xs || (a == xs && pos0 + j < x)) ? step : 0;
+      }
+      const float a = ls[lo];
+      lo += (a > xs || (a == xs && pos0 + lo < x)) ? 1 : 0;
+      rank += lo;
+    }
+    if (rank < K) {
+      const int r = s_li[x];
+      cand_score[out_base + rank] = xs;
+      cand_idx[out_base + rank] = r < 0 ? -1LL : row_base + (long long)r;
+    }
+  }
+}
+
 // ===========================================================================
 // Host wrappers
 // ===========================================================================
@@ -598,95 +792,69 @@ std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
   return {out_s, out_i};
 }
 
+
 // ---------------------------------------------------------------------------
 // IVF scan + merge. probes [Q][P] int32 (any value outside [0, C) skips);
 // list_off [C+1] / list_rows [M] int32 CSR of slot numbers below tail_start;
 // rows [tail_start, N) are scanned by every query. max_len is the longest
 // list, recorded when the lists were built (no device sync per search).
+// ivf_scan (bf16), ivf_scan_i8 and ivf_scan_fp8 share the argument checks,
+// the grid and the merge; they differ in the corpus / query dtype and in
+// the scan kernel.
 // ---------------------------------------------------------------------------
-template <int K>
-static void ivf_scan_launch(const at::Tensor& db, const at::Tensor& q,
-                            const at::Tensor& probes,
-                            const at::Tensor& list_off,
-                            const at::Tensor& list_rows, int p_eff, int split,
-                            int tail_start, long long row_base, int k_out,
-                            const unsigned int* allow_p, at::Tensor& out_s,
-                            at::Tensor& out_i) {
-  const int n = (int)db.size(0);
-  const int d = (int)db.size(1);
-  const int qc = (int)q.size(0);
-  const int n_probe = (int)probes.size(1);
-  const long long w = (long long)p_eff * split;
-  at::Tensor cand_s = at::empty({w, qc, K}, out_s.options());
-  at::Tensor cand_i = at::empty({w, qc, K}, out_i.options());
-  const size_t lds = (size_t)d * 2 + (size_t)16 * K * 8;
-  TORCH_CHECK(lds <= 64 * 1024, "ivf_scan: D too large for the LDS query tile");
-  auto launch = allow_p ? k_ivf_scan_bf16<K, true> : k_ivf_scan_bf16<K, false>;
-  hipLaunchKernelGGL(launch, dim3((unsigned)(w * qc)), dim3(256), lds,
-                     cur_stream(), (const unsigned short*)db.data_ptr(),
-                     (const unsigned short*)q.data_ptr(),
-                     probes.data_ptr<int>(), list_off.data_ptr<int>(),
-                     list_rows.data_ptr<int>(), (int)list_off.numel() - 1,
-                     (long long)list_rows.numel(), n_probe, p_eff, split,
-                     tail_start, n, d, qc, row_base,
-                     cand_s.data_ptr<float>(),
-                     reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()),
-                     allow_p);
-  HIP_CHECK_LAST();
-  hipLaunchKernelGGL((k_topk_merge<K>), dim3(qc), dim3(256), 0, cur_stream(),
-                     cand_s.data_ptr<float>(),
-                     reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()),
-                     w, qc, k_out, out_s.data_ptr<float>(),
-                     reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()));
-  HIP_CHECK_LAST();
-}
+struct IvfPlan {
+  int n, d, qc, n_probe, p_eff, split, tail_start, k_out;
+  long long row_base;
+  const unsigned int* allow_p;
+};
 
-std::tuple<at::Tensor, at::Tensor> ivf_scan(
-    at::Tensor db, at::Tensor q, at::Tensor probes, at::Tensor list_off,
-    at::Tensor list_rows, long long tail_start, long long max_len,
-    long long row_base, int k_out, c10::optional<at::Tensor> allow) {
+// Validates the arguments every IVF scan takes and sizes the grid. A
+// p_eff of 0 means there is nothing to scan.
+static IvfPlan ivf_scan_plan(const char* who, const at::Tensor& db,
+                             at::ScalarType db_type, const char* db_name,
+                             const at::Tensor& q, at::ScalarType q_type,
+                             const at::Tensor& probes,
+                             const at::Tensor& list_off,
+                             const at::Tensor& list_rows, long long tail_start,
+                             long long max_len, long long row_base, int k_out,
+                             const c10::optional<at::Tensor>& allow) {
   TORCH_CHECK(db.is_cuda() && db.dim() == 2 && db.is_contiguous() &&
-                  db.scalar_type() == at::kBFloat16,
-              "ivf_scan: db must be contiguous 2D bf16 CUDA");
+                  db.scalar_type() == db_type,
+              who, ": db must be contiguous 2D ", db_name, " CUDA");
   TORCH_CHECK(q.is_cuda() && q.dim() == 2 && q.is_contiguous() &&
-                  q.scalar_type() == at::kBFloat16,
-              "ivf_scan: q must be contiguous 2D bf16 CUDA");
+                  q.scalar_type() == q_type,
+              who, ": q must be contiguous 2D ", db_name, " CUDA");
   for (const at::Tensor* t : {&probes, &list_off, &list_rows})
     TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
                     t->scalar_type() == at::kInt,
-                "ivf_scan: probes, list_off and list_rows must be contiguous "
+                who, ": probes, list_off and list_rows must be contiguous "
                 "int32 CUDA tensors");
   TORCH_CHECK(q.device() == db.device() && probes.device() == db.device() &&
                   list_off.device() == db.device() &&
                   list_rows.device() == db.device(),
-              "ivf_scan: all tensors must be on db's device");
+              who, ": all tensors must be on db's device");
   const long long n = db.size(0);
   const int d = (int)db.size(1);
   const long long qc = q.size(0);
-  TORCH_CHECK(q.size(1) == d, "ivf_scan: dim mismatch");
-  TORCH_CHECK(d % 128 == 0, "ivf_scan needs D % 128 == 0");
-  TORCH_CHECK(n <= 0x7fffffffLL, "ivf_scan: int32 slot numbers, N < 2^31");
-  TORCH_CHECK(qc >= 1, "ivf_scan: need at least one query");
+  TORCH_CHECK(q.size(1) == d, who, ": dim mismatch");
+  TORCH_CHECK(d % 128 == 0, who, " needs D % 128 == 0");
+  TORCH_CHECK(n <= 0x7fffffffLL, who, ": int32 slot numbers, N < 2^31");
+  TORCH_CHECK(qc >= 1, who, ": need at least one query");
   TORCH_CHECK(probes.dim() == 2 && probes.size(0) == qc,
-              "ivf_scan: probes must be [Q, P]");
+              who, ": probes must be [Q, P]");
   TORCH_CHECK(list_off.dim() == 1 && list_off.numel() >= 1 &&
                   list_rows.dim() == 1,
-              "ivf_scan: list_off must be [C+1] and list_rows [M]");
+              who, ": list_off must be [C+1] and list_rows [M]");
   TORCH_CHECK(tail_start >= 0 && tail_start <= n,
-              "ivf_scan: tail_start must be in [0, N]");
-  TORCH_CHECK(max_len >= 0, "ivf_scan: max_len must be >= 0");
-  TORCH_CHECK(k_out >= 1 && k_out <= 64, "ivf_scan: k_out must be in 1..64");
+              who, ": tail_start must be in [0, N]");
+  TORCH_CHECK(max_len >= 0, who, ": max_len must be >= 0");
+  TORCH_CHECK(k_out >= 1 && k_out <= 64, who, ": k_out must be in 1..64");
   const unsigned int* allow_p = nullptr;
-  if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "ivf_scan");
+  if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, who);
 
-  auto opts_f = db.options().dtype(at::kFloat);
-  auto opts_i = db.options().dtype(at::kLong);
   const long long n_probe = probes.size(1);
   const long long tail_len = n - tail_start;
   const long long p_eff = n_probe + (tail_len > 0 ? 1 : 0);
-  if (p_eff == 0)
-    return {at::full({qc, (long long)k_out}, -1e30f, opts_f),
-            at::full({qc, (long long)k_out}, -1LL, opts_i)};
 
   // ~4 blocks per CU over the whole grid, but every split of the longest
   // list keeps at least block_rows rows: each block adds one candidate
@@ -696,19 +864,149 @@ std::tuple<at::Tensor, at::Tensor> ivf_scan(
   if (const char* g = getenv("NORNICDB_IVF_BLOCK_ROWS"))
     block_rows = std::max(atoi(g), 1);
   const long long longest = std::max<long long>(std::max(max_len, tail_len), 1);
-  long long split = std::max<long long>(1024 / (qc * p_eff), 1);
-  split = std::min(split, (longest + block_rows - 1) / block_rows);
-  TORCH_CHECK(qc * p_eff * split <= 0x7fffffffLL, "ivf_scan: grid too large");
+  long long split = 1;
+  if (p_eff > 0) {
+    split = std::max<long long>(1024 / (qc * p_eff), 1);
+    split = std::min(split, (longest + block_rows - 1) / block_rows);
+    TORCH_CHECK(qc * p_eff * split <= 0x7fffffffLL, who, ": grid too large");
+  }
+  return {(int)n, d, (int)qc, (int)n_probe, (int)p_eff, (int)split,
+          (int)tail_start, k_out, row_base, allow_p};
+}
 
-  at::Tensor out_s = at::empty({qc, (long long)k_out}, opts_f);
-  at::Tensor out_i = at::empty({qc, (long long)k_out}, opts_i);
-  if (k_out <= 16)
-    ivf_scan_launch<16>(db, q, probes, list_off, list_rows, (int)p_eff,
-                        (int)split, (int)tail_start, row_base, k_out, allow_p,
-                        out_s, out_i);
-  else
-    ivf_scan_launch<64>(db, q, probes, list_off, list_rows, (int)p_eff,
-                        (int)split, (int)tail_start, row_base, k_out, allow_p,
-                        out_s, out_i);
+// Allocates the [W][Q][K] candidates, has `scan(blocks, lds_bytes, cand_s,
+// cand_i)` launch the scan kernel over them (q_bytes of LDS hold the
+// query) and merges them into [Q][k_out].
+template <int K, typename Scan>
+static std::tuple<at::Tensor, at::Tensor> ivf_scan_merge(
+    const char* who, const IvfPlan& pl, const at::Tensor& db, size_t q_bytes,
+    Scan scan) {
+  auto opts_f = db.options().dtype(at::kFloat);
+  auto opts_i = db.options().dtype(at::kLong);
+  const long long w = (long long)pl.p_eff * pl.split;
+  at::Tensor out_s = at::empty({pl.qc, pl.k_out}, opts_f);
+  at::Tensor out_i = at::empty({pl.qc, pl.k_out}, opts_i);
+  at::Tensor cand_s = at::empty({w, pl.qc, K}, opts_f);
+  at::Tensor cand_i = at::empty({w, pl.qc, K}, opts_i);
+  const size_t lds = q_bytes + (size_t)16 * K * 8;
+  TORCH_CHECK(lds <= 64 * 1024, who, ": D too large for the LDS query tile");
+  scan(dim3((unsigned)(w * pl.qc)), lds, cand_s.data_ptr<float>(),
+       reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()));
+  HIP_CHECK_LAST();
+  hipLaunchKernelGGL((k_topk_merge<K>), dim3(pl.qc), dim3(256), 0,
+                     cur_stream(), cand_s.data_ptr<float>(),
+                     reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()),
+                     w, pl.qc, pl.k_out, out_s.data_ptr<float>(),
+                     reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()));
+  HIP_CHECK_LAST();
   return {out_s, out_i};
+}
+
+static std::tuple<at::Tensor, at::Tensor> ivf_nothing_to_scan(
+    const IvfPlan& pl, const at::Tensor& db) {
+  return {at::full({pl.qc, pl.k_out}, -1e30f, db.options().dtype(at::kFloat)),
+          at::full({pl.qc, pl.k_out}, -1LL, db.options().dtype(at::kLong))};
+}
+
+template <int K>
+static std::tuple<at::Tensor, at::Tensor> ivf_scan_bf16_run(
+    const IvfPlan& pl, const at::Tensor& db, const at::Tensor& q,
+    const at::Tensor& probes, const at::Tensor& list_off,
+    const at::Tensor& list_rows) {
+  auto kern = pl.allow_p ? k_ivf_scan_bf16<K, true> : k_ivf_scan_bf16<K, false>;
+  return ivf_scan_merge<K>(
+      "ivf_scan", pl, db, (size_t)pl.d * 2,
+      [&](dim3 grid, size_t lds, float* cand_s, long long* cand_i) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, cur_stream(),
+                           (const unsigned short*)db.data_ptr(),
+                           (const unsigned short*)q.data_ptr(),
+                           probes.data_ptr<int>(), list_off.data_ptr<int>(),
+                           list_rows.data_ptr<int>(),
+                           (int)list_off.numel() - 1,
+                           (long long)list_rows.numel(), pl.n_probe, pl.p_eff,
+                           pl.split, pl.tail_start, pl.n, pl.d, pl.qc,
+                           pl.row_base, cand_s, cand_i, pl.allow_p);
+      });
+}
+
+std::tuple<at::Tensor, at::Tensor> ivf_scan(
+    at::Tensor db, at::Tensor q, at::Tensor probes, at::Tensor list_off,
+    at::Tensor list_rows, long long tail_start, long long max_len,
+    long long row_base, int k_out, c10::optional<at::Tensor> allow) {
+  const IvfPlan pl = ivf_scan_plan("ivf_scan", db, at::kBFloat16, "bf16", q,
+                                   at::kBFloat16, probes, list_off, list_rows,
+                                   tail_start, max_len, row_base, k_out, allow);
+  if (pl.p_eff == 0) return ivf_nothing_to_scan(pl, db);
+  if (k_out <= 16)
+    return ivf_scan_bf16_run<16>(pl, db, q, probes, list_off, list_rows);
+  return ivf_scan_bf16_run<64>(pl, db, q, probes, list_off, list_rows);
+}
+
+// sa / sq are null for fp8
+template <int K, int FMT>
+static std::tuple<at::Tensor, at::Tensor> ivf_scan_q8_run(
+    const char* who, const IvfPlan& pl, const at::Tensor& db,
+    const at::Tensor& q, const float* sa, const float* sq,
+    const at::Tensor& probes, const at::Tensor& list_off,
+    const at::Tensor& list_rows) {
+  auto kern = pl.allow_p ? k_ivf_scan_q8<K, true, FMT>
+                         : k_ivf_scan_q8<K, false, FMT>;
+  return ivf_scan_merge<K>(
+      who, pl, db, (size_t)pl.d,
+      [&](dim3 grid, size_t lds, float* cand_s, long long* cand_i) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, cur_stream(),
+                           (const unsigned char*)db.data_ptr(),
+                           (const unsigned char*)q.data_ptr(), sa, sq,
+                           probes.data_ptr<int>(), list_off.data_ptr<int>(),
+                           list_rows.data_ptr<int>(),
+                           (int)list_off.numel() - 1,
+                           (long long)list_rows.numel(), pl.n_probe, pl.p_eff,
+                           pl.split, pl.tail_start, pl.n, pl.d, pl.qc,
+                           pl.row_base, cand_s, cand_i, pl.allow_p);
+      });
+}
+
+std::tuple<at::Tensor, at::Tensor> ivf_scan_i8(
+    at::Tensor db, at::Tensor sa, at::Tensor q, at::Tensor sq,
+    at::Tensor probes, at::Tensor list_off, at::Tensor list_rows,
+    long long tail_start, long long max_len, long long row_base, int k_out,
+    c10::optional<at::Tensor> allow) {
+  const char* who = "ivf_scan_i8";
+  const IvfPlan pl = ivf_scan_plan(who, db, at::kChar, "int8", q, at::kChar,
+                                   probes, list_off, list_rows, tail_start,
+                                   max_len, row_base, k_out, allow);
+  for (const at::Tensor* t : {&sa, &sq})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == at::kFloat &&
+                    t->device() == db.device(),
+                who, ": sa and sq must be contiguous fp32 tensors on db's "
+                "device");
+  TORCH_CHECK(sa.numel() == pl.n, who, ": sa must hold one scale per row, N");
+  TORCH_CHECK(sq.numel() == pl.qc, who,
+              ": sq must hold one scale per query, Q");
+  if (pl.p_eff == 0) return ivf_nothing_to_scan(pl, db);
+  const float* sap = sa.data_ptr<float>();
+  const float* sqp = sq.data_ptr<float>();
+  if (k_out <= 16)
+    return ivf_scan_q8_run<16, IVF_FMT_I8>(who, pl, db, q, sap, sqp, probes,
+                                           list_off, list_rows);
+  return ivf_scan_q8_run<64, IVF_FMT_I8>(who, pl, db, q, sap, sqp, probes,
+                                         list_off, list_rows);
+}
+
+std::tuple<at::Tensor, at::Tensor> ivf_scan_fp8(
+    at::Tensor db, at::Tensor q, at::Tensor probes, at::Tensor list_off,
+    at::Tensor list_rows, long long tail_start, long long max_len,
+    long long row_base, int k_out, c10::optional<at::Tensor> allow) {
+  const char* who = "ivf_scan_fp8";
+  const IvfPlan pl = ivf_scan_plan(who, db, at::kByte, "uint8 (e4m3 bytes)", q,
+                                   at::kByte, probes, list_off, list_rows,
+                                   tail_start, max_len, row_base, k_out,
+                                   allow);
+  if (pl.p_eff == 0) return ivf_nothing_to_scan(pl, db);
+  if (k_out <= 16)
+    return ivf_scan_q8_run<16, IVF_FMT_FP8>(who, pl, db, q, nullptr, nullptr,
+                                            probes, list_off, list_rows);
+  return ivf_scan_q8_run<64, IVF_FMT_FP8>(who, pl, db, q, nullptr, nullptr,
+                                          probes, list_off, list_rows);
 }

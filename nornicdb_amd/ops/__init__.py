@@ -42,5 +42,6 @@ from .knn import (  # noqa: E402,F401
     knn_search, knn_search_exact, pack_allow_mask, unpack_allow_mask,
 )
 from .ivf import (  # noqa: E402,F401
-    IVFLists, ivf_build_lists, ivf_route, ivf_search, ivf_search_exact,
+    IVFLists, ivf_build_lists, ivf_route, ivf_route_kind, ivf_search,
+    ivf_search_exact,
 )

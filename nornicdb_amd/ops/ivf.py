@@ -6,10 +6,15 @@ numbers (`IVFLists.list_rows[list_off[c]:list_off[c + 1]]`), all below
 `n_built`; rows `[tail_start, N)` were appended after the lists were built
 and are scanned by every query as one extra pseudo-list.
 
-- GPU, bf16, D % 128 == 0, k <= 64: the fused HIP kernel `ivf_scan`
-  (csrc/vector_ops.hip) gathers, scores and top-k's the probed rows;
-- GPU otherwise (fp8 / int8 corpora, odd D, larger k): a torch gather
-  fallback (index_select of the candidate rows, matmul, top-k);
+Routes (`ivf_route_kind`), on the GPU with D % 128 == 0 and k <= 64:
+- bf16: the fused HIP kernel `ivf_scan` (csrc/vector_ops.hip) gathers,
+  scores and top-k's the probed rows;
+- int8 with per-row scales: `ivf_scan_i8`, the same block contract on
+  1-byte rows (exact int32 dot * sa[row] * sq[query]); the query is
+  quantised in torch first, as `knn_search_int8` does;
+- fp8 e4m3: `ivf_scan_fp8`, fp32 accumulation of the converted bytes;
+- GPU otherwise (fp32 corpora, odd D, larger k): a torch gather fallback
+  (index_select of the candidate rows, matmul, top-k);
 - CPU: `ivf_search_exact`, which is also the numerics oracle.
 
 Probes of one query are a set: -1 (or any id outside [0, C)) skips, and a
@@ -85,6 +90,16 @@ def ivf_route(lists: IVFLists, q: torch.Tensor, nprobe: int) -> torch.Tensor:
     score = torch.addmm(cn, qf, c.T, beta=-1.0, alpha=2.0)
     return torch.topk(score, min(nprobe, c.shape[0]), dim=-1) \
         .indices.to(torch.int32)
+
+
+def ivf_route_kind(dtype: torch.dtype, d: int, k: int) -> str:
+    """Which GPU route scores a corpus of this dtype, row width and top-k:
+    "scan" (bf16), "scan_i8", "scan_fp8" (the fused kernels) or "gather"
+    (the torch fallback)."""
+    if d % 128 != 0 or k > IVF_MAX_K:
+        return "gather"
+    return {torch.bfloat16: "scan", torch.int8: "scan_i8",
+            torch.float8_e4m3fn: "scan_fp8"}.get(dtype, "gather")
 
 
 def _query_values(db, q):
@@ -240,14 +255,23 @@ def ivf_search(
     nat = native_or_none()
     if nat is None:
         require_native()  # raises: no eager fallback on GPU
-    if db.dtype == torch.bfloat16 and db.shape[1] % 128 == 0 \
-            and k <= IVF_MAX_K:
-        words = None if allow is None else _mask_words(allow, n)
+    kind = ivf_route_kind(db.dtype, db.shape[1], k)
+    if kind == "gather":
+        return _ivf_gather(db, q, k, lists, probes, tail_start, row_base,
+                           allow, scales)
+    words = None if allow is None else _mask_words(allow, n)
+    tail = (probes.to(torch.int32).contiguous(), lists.list_off,
+            lists.list_rows, tail_start, lists.max_len, row_base, k, words)
+    if kind == "scan":
         s, i = nat.ivf_scan(db.contiguous(),
-                            q.to(torch.bfloat16).contiguous(),
-                            probes.to(torch.int32).contiguous(),
-                            lists.list_off, lists.list_rows, tail_start,
-                            lists.max_len, row_base, k, words)
-        return _pad_unfilled(s, i)
-    return _ivf_gather(db, q, k, lists, probes, tail_start, row_base, allow,
-                       scales)
+                            q.to(torch.bfloat16).contiguous(), *tail)
+    elif kind == "scan_i8":
+        # the query is quantised here, as in knn_search_int8, so every
+        # route scores identical values
+        qi, sq = quantize_int8(q)
+        s, i = nat.ivf_scan_i8(db.contiguous(), scales.float().contiguous(),
+                               qi.contiguous(), sq.contiguous(), *tail)
+    else:
+        qb = q.to(torch.float8_e4m3fn).contiguous().view(torch.uint8)
+        s, i = nat.ivf_scan_fp8(db.contiguous().view(torch.uint8), qb, *tail)
+    return _pad_unfilled(s, i)

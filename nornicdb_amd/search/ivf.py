@@ -4,8 +4,9 @@
 inverted lists of slot numbers on the embedding index's device
 (ops.ivf.IVFLists). A search routes the query to its `nprobe` nearest
 centroids and scores only those lists plus the tail, the slots appended
-since the build, with the fused `ivf_scan` kernel on the GPU. The corpus
-is not copied or reordered, and the index's own live mask (ANDed with any
+since the build, with a fused scan kernel on the GPU: `ivf_scan` for a
+bf16 corpus, `ivf_scan_i8` / `ivf_scan_fp8` for the quantised modes
+(ops.ivf.ivf_route_kind). The corpus is not copied or reordered, and the index's own live mask (ANDed with any
 `allow_ids`) is the kernel's allow mask, so removed ids are never returned
 and never widen k.
 

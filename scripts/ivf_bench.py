@@ -17,6 +17,14 @@ Timing: device events around `--iters` back-to-back calls per sample, after
 a warm-up of every variant; the variants alternate inside each of
 `--repeats` rounds. The table gives the median sample and min..max in ms
 per call. A run without a GPU is refused unless --rehearse is given.
+
+`--quant int8|fp8` quantises the same corpus (lists are still built from
+the bf16 rows) and times, for every IVF variant, `ivf_search` (the fused
+`ivf_scan_i8` / `ivf_scan_fp8` route, query quantisation included), the
+kernel pair alone on a query quantised beforehand, and the torch gather
+route (`ops.ivf._ivf_gather`) that scored these corpora before the kernels
+existed. Bytes scanned are then rows times D (plus 4 per row for int8
+scales).
 """
 
 import argparse
@@ -38,6 +46,8 @@ def main():
     p.add_argument("--kmeans-iters", type=int, default=4)
     p.add_argument("--iters", type=int, default=50, help="calls per sample")
     p.add_argument("--repeats", type=int, default=7, help="samples per variant")
+    p.add_argument("--quant", choices=["bf16", "int8", "fp8"], default="bf16",
+                   help="corpus format; int8 / fp8 also time the gather route")
     p.add_argument("--rehearse", action="store_true",
                    help="run the host logic on the CPU at a tiny shape")
     args = p.parse_args()
@@ -45,6 +55,8 @@ def main():
     from nornicdb_amd import ops
     from nornicdb_amd.ops import (ivf_build_lists, ivf_route, ivf_search,
                                   knn_search)
+    from nornicdb_amd.ops.ivf import _ivf_gather, ivf_route_kind
+    from nornicdb_amd.ops.knn import quantize_fp8, quantize_int8
     from nornicdb_amd.search.kmeans import kmeans, optimal_k
 
     if args.rehearse:
@@ -93,40 +105,92 @@ def main():
     build_s = time.perf_counter() - t0
     lens = (lists.list_off[1:] - lists.list_off[:-1]).cpu()
 
+    quant = args.quant != "bf16"
+    scales = None
+    qdtype = db.dtype
+    row_bytes = d * db.element_size()
+    if quant:
+        # quantise in slabs: the fp32 temporaries of a 4M-row corpus at once
+        # would be several times the corpus
+        store = torch.empty(n, d, device=device, dtype=torch.int8
+                            if args.quant == "int8" else torch.float8_e4m3fn)
+        if args.quant == "int8":
+            scales = torch.empty(n, device=device)
+        for r0 in range(0, n, 1 << 18):
+            sl = slice(r0, min(r0 + (1 << 18), n))
+            if args.quant == "int8":
+                store[sl], scales[sl] = quantize_int8(db[sl])
+            else:
+                store[sl] = quantize_fp8(db[sl])
+        db = store
+        row_bytes = d + (4 if args.quant == "int8" else 0)
+        sync()
+
+    def search(q, kk, probes):
+        return ivf_search(db, q, kk, lists, probes, n, scales=scales)
+
+    def gather(q, kk, probes):
+        return _ivf_gather(db, q, kk, lists, probes, n, 0, None, scales)
+
+    def kernels_only(q, kk, probes):
+        """The scan + merge pair on a query that is already quantised."""
+        nat = ops.require_native()
+        tail = (probes, lists.list_off, lists.list_rows, n, lists.max_len, 0,
+                kk, None)
+        if args.quant == "int8":
+            qi, sq = quantize_int8(q)
+            return lambda: nat.ivf_scan_i8(db, scales, qi, sq, *tail)
+        qb = q.to(torch.float8_e4m3fn).view(torch.uint8)
+        dbb = db.view(torch.uint8)
+        return lambda: nat.ivf_scan_fp8(dbb, qb, *tail)
+
     variants = {}
     meta = {}
     for qn, nprobe in ((1, 1), (1, 8), (1, 32), (16, 8)):
         g = torch.Generator(device=device).manual_seed(qn)
         q = torch.nn.functional.normalize(
             torch.randn(qn, d, device=device, generator=g), dim=-1) \
-            .to(db.dtype)
+            .to(qdtype)
         probes = ivf_route(lists, q, nprobe)
         rows = int(lens[probes.cpu().long()].sum())
         name = f"ivf Q={qn} nprobe={nprobe}"
         meta[name] = {"Q": qn, "nprobe": nprobe, "rows_scanned": rows,
-                      "bytes_scanned": rows * d * db.element_size()}
+                      "bytes_scanned": rows * row_bytes}
         variants[name + " route"] = \
             (lambda q=q, nprobe=nprobe: ivf_route(lists, q, nprobe))
         variants[name + " scan+merge"] = \
-            (lambda q=q, probes=probes: ivf_search(db, q, k, lists, probes, n))
+            (lambda q=q, probes=probes: search(q, k, probes))
         variants[name + " total"] = \
-            (lambda q=q, nprobe=nprobe: ivf_search(
-                db, q, k, lists, ivf_route(lists, q, nprobe), n))
-        s, i = ivf_search(db, q, k, lists, probes, n)
+            (lambda q=q, nprobe=nprobe: search(
+                q, k, ivf_route(lists, q, nprobe)))
+        s, i = search(q, k, probes)
         assert s.shape == (qn, min(k, n)) and (i >= 0).all()
+        ks = [k]
         if (qn, nprobe) == (1, 8):
             # hybrid search's over-fetch size: the K=64 instantiation
             meta[name + " k=40"] = dict(meta[name])
             variants[name + " k=40 scan+merge"] = \
-                (lambda q=q, probes=probes: ivf_search(db, q, 40, lists,
-                                                       probes, n))
+                (lambda q=q, probes=probes: search(q, 40, probes))
+            ks.append(40)
+        for kk in ks if quant else ():
+            tag = name + ("" if kk == k else f" k={kk}")
+            meta.setdefault(tag, dict(meta[name]))
+            if on_gpu:
+                assert ivf_route_kind(db.dtype, d, kk) != "gather"
+                variants[tag + " kernels"] = kernels_only(q, kk, probes)
+            variants[tag + " gather"] = \
+                (lambda q=q, probes=probes, kk=kk: gather(q, kk, probes))
+            gs, gi = gather(q, kk, probes)
+            ss, si = search(q, kk, probes)
+            assert (gs - ss).abs().max() <= 1e-4, "routes disagree"
         if qn == 1:
             bq = q
         else:
             bq16 = q
-    variants["brute Q=1"] = lambda: knn_search(db, bq, k)
-    variants["brute Q=16"] = lambda: knn_search(db, bq16, k)
-    variants["brute Q=1 k=40"] = lambda: knn_search(db, bq, 40)
+    if not quant:
+        variants["brute Q=1"] = lambda: knn_search(db, bq, k)
+        variants["brute Q=16"] = lambda: knn_search(db, bq16, k)
+        variants["brute Q=1 k=40"] = lambda: knn_search(db, bq, 40)
     full = n * d * db.element_size()
 
     for fn in variants.values():          # warm every variant
@@ -139,9 +203,9 @@ def main():
             samples[name].append(timed(fn))
 
     med = {name: statistics.median(xs) for name, xs in samples.items()}
-    print(f"# {n} x {d} bf16, C={lists.n_lists} (max list {lists.max_len}, "
-          f"mean {n / lists.n_lists:.0f}), k={k}, {args.iters} calls/sample, "
-          f"{args.repeats} samples, device={device}, lists built in "
+    print(f"# {n} x {d} {args.quant}, C={lists.n_lists} "
+          f"(max list {lists.max_len}, mean {n / lists.n_lists:.0f}), "
+          f"k={k}, {args.iters} calls/sample, {args.repeats} samples, device={device}, lists built in "
           f"{build_s:.1f} s"
           + (" (REHEARSAL: not a measurement)" if not on_gpu else ""))
     print("| variant | ms/call median | min..max | MB scanned | GB/s |")
@@ -150,7 +214,7 @@ def main():
     for name, xs in samples.items():
         base = name.rsplit(" ", 1)[0]
         nbytes = None
-        if name.endswith("scan+merge"):
+        if name.endswith(("scan+merge", "kernels", "gather")):
             nbytes = meta[base]["bytes_scanned"]
         elif name.startswith("brute"):
             nbytes = full
@@ -161,7 +225,8 @@ def main():
         out.append({"variant": name, "ms_median": round(med[name], 5),
                     "ms_min": round(min(xs), 5), "ms_max": round(max(xs), 5),
                     "bytes": nbytes})
-    print(json.dumps({"rows": n, "dim": d, "k": k, "lists": lists.n_lists,
+    print(json.dumps({"rows": n, "dim": d, "k": k, "quant": args.quant,
+                      "lists": lists.n_lists,
                       "max_len": lists.max_len, "device": str(device),
                       "rehearsal": not on_gpu, "variants": meta,
                       "results": out}))
