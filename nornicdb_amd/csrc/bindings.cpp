@@ -23,6 +23,7 @@ std::tuple<at::Tensor, at::Tensor> ivf_scan_fp8(
 
 // knn_mfma.hip
 long long knn_bm_value();
+long long knn_rg_value();
 #define KNN_BM_VALUE knn_bm_value()
 std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
                                             long long row_base, int k_out,
@@ -126,7 +127,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("list_rows"), py::arg("tail_start"), py::arg("max_len"),
         py::arg("row_base") = 0, py::arg("k_out") = 10,
         py::arg("allow") = c10::nullopt);
+  // KNN_BM: rows of one kNN panel; KNN_RG: row groups the panel is made of
   m.attr("KNN_BM") = KNN_BM_VALUE;
+  m.attr("KNN_RG") = knn_rg_value();
   m.def("knn_mfma", &knn_mfma,
         "Fused MFMA cosine score + top-k, 256-query batches (bf16 db)",
         py::arg("db"), py::arg("q"), py::arg("row_base") = 0,

@@ -6,21 +6,29 @@
 // exactly once per query batch.
 //
 // Structure (history of the measurements: profiles/README.md):
-//   * 160x256 output tile, 4 waves (256 thr), 2 workgroups/CU (62 KB LDS,
-//     233 VGPRs, no spills). The kernel is bound by what a CU can ingest:
-//     every corpus byte (HBM) drags 256*2/BM bytes of query tile (L2)
-//     through the same load path, 2.67 B at 96 rows and 1.6 B at 160.
-//     Taller tiles are what buys speed; the software pipeline below is
-//     what lets two workgroups per CU keep that path busy, where the
-//     synchronous loop needed three co-resident ones to overlap at all.
+//   * a workgroup is KNN_RG row groups of KNN_BM = 160 corpus rows, four
+//     waves each: wave w owns row group w >> 2 and query quarter w & 3
+//     (64 columns), a 160x64 accumulator tile (233 VGPRs, no spills). The
+//     panel is KNN_RG * 160 rows. KNN_RG = 2 (default): 8 waves, 320x256
+//     output tile, one workgroup per CU. KNN_RG = 1: 4 waves, 160x256, two
+//     workgroups per CU. Either way a CU holds 320 x 256 fp32 accumulators
+//     in 8 waves; what differs is how often the query tile is staged.
+//     The kernel is bound by what a CU can ingest: every corpus byte (HBM)
+//     drags 256*2/panel bytes of query tile (L2) through the same load
+//     path, 2.67 B at 96 rows, 1.6 B at 160, 0.8 B at 320. With KNN_RG = 2
+//     both row groups read one staged copy of the query stage where two
+//     independent workgroups each staged their own.
 //   * one flat stream of BK=32 stages per workgroup: the (panel, k) loops
 //     are flattened, stage g = (panel, 32-wide K slice). Per stage a wave
 //     runs 40 mfma_f32_16x16x32_bf16 (ascending k per accumulator, the
-//     same order as a BK=64 loop, so scores do not depend on the staging).
-//   * LDS: query tile double-buffered (2 x 16 KB), corpus tile in a ring of
-//     three 10 KB buffers; staged by __builtin_amdgcn_global_load_lds width
-//     16. While stage g computes, the queries of stage g+1 (L2-resident)
-//     and the corpus rows of stages g+1 and g+2 (the HBM stream) are in
+//     same order as a BK=64 loop, so scores do not depend on the staging
+//     or on KNN_RG).
+//   * LDS (one array): query tile double-buffered (2 x 16 KB), corpus tile
+//     in a ring of three buffers of panel x 64 B (20 KB at 320 rows), then
+//     the epilogue region, 4 KB per wave: 124 KB at KNN_RG = 2, 78 KB at
+//     KNN_RG = 1. Staged by __builtin_amdgcn_global_load_lds width 16.
+//     While stage g computes, the queries of stage g+1 (L2-resident) and
+//     the corpus rows of stages g+1 and g+2 (the HBM stream) are in
 //     flight; the corpus prefetch crosses the panel boundary, so it also
 //     runs under the top-k epilogue.
 //   * stage rows are 64 B; 16 B-slot XOR swizzle, applied to the global
@@ -30,36 +38,47 @@
 //     accesses or __syncthreads() hipcc waits vmcnt(0) while an LDS-DMA is
 //     outstanding and the prefetch drains every stage.
 //   * transposed epilogue: acc fragments go 16 rows at a time through a
-//     [col][16] fp32 block that lives in the query buffer the last stage
-//     just read (the other one is receiving the next stage's queries);
-//     each thread owns one query column and keeps a register top-K list
-//     (statically unrolled insertion).
+//     [col][16] fp32 block; each thread owns one (row group, query column)
+//     pair and keeps a register top-K list (statically unrolled insertion).
+//     The epilogue has no barrier (see "Epilogue privacy" below).
 //   * corpus loads use the default cache policy: non-temporal (aux = 2)
 //     measured 22 % slower (81.8 vs 67.1 ms at 100M rows, 96-row tile).
-//   KNN_BM=96 builds the same kernel at 3 workgroups/CU (50 KB LDS, 161
-//   VGPRs); it measured within 2 % of the synchronous 96-row loop.
 //
-// Pipeline ordering (VM loads retire in order; counts are per wave):
-//   stage g issues  B(g+1)  NB = 4 instructions   -> sB[(g+1)&1]
-//          then     A(g+2)  NA = 3 instructions   -> sA[(g+2)%3]
-//   (NB = 256 query rows / 16 rows per 1 KB piece / 4 waves; NA = BM/16
-//   pieces over 4 waves: 10 pieces = 2 whole + 1 half piece per wave)
+// Pipeline ordering (VM loads retire in order; counts are per wave, W =
+// 4 * KNN_RG waves; numbers for W = 8, in brackets for W = 4):
+//   stage g issues  B(g+1)  NB = 2 [4] instructions  -> sB[(g+1)&1]
+//          then     A(g+2)  NA = 3 instructions      -> sA[(g+2)%3]
+//   (NB = 256 query rows / 16 rows per 1 KB piece / W waves; NA = panel/16
+//   pieces over W waves: 20 [10] pieces = 2 whole pieces per wave + one
+//   8-row half piece per wave)
 //   and ends with   s_waitcnt vmcnt(NA); s_barrier.
 //   At that wait the wave's queue holds, oldest first,
-//     A(g+1) [issued in stage g-1, after B(g)], B(g+1), A(g+2),
-//   everything older having been retired by stage g-1's wait. vmcnt(NA)
-//   therefore retires A(g+1) and B(g+1) and leaves only A(g+2) in flight.
-//   An A(g+1)-before-B(g) order would need a wait that also drains the
-//   newest prefetch; issuing the prefetch LAST is what keeps it in flight.
+//     A(g+1)[3] (issued in stage g-1, after B(g)), B(g+1)[2 or 4], A(g+2)[3],
+//   everything older having been retired by stage g-1's wait. vmcnt(NA) =
+//   vmcnt(3) therefore retires A(g+1) and B(g+1) and leaves exactly A(g+2)
+//   in flight, whatever NB is. An A(g+1)-before-B(g) order would need a
+//   wait that also drains the newest prefetch; issuing the prefetch LAST
+//   is what keeps it in flight.
 //   Read-after-DMA: stage g+1 reads sB[(g+1)&1] and sA[(g+1)%3] after the
 //   barrier that follows that wait in every wave, so every wave's pieces
-//   have landed. Write-after-read: B(g+1) and A(g+2) overwrite the buffers
-//   stage g-1 read; every wave retired those ds_reads (lgkmcnt(0) ahead of
-//   its last MFMA group) before it arrived at stage g-1's end barrier.
-//   The epilogue block reuses sB[g&1] after stage g's end barrier and is
-//   followed by a barrier of its own before stage g+1 restages that buffer;
-//   no DMA targets sB[g&1] in between (B(g+1) went to the other buffer,
-//   A lives in its own ring).
+//   have landed (a wave reads query pieces staged by its partner wave of
+//   the other row group, and corpus pieces staged by any wave). Write-
+//   after-read: B(g+1) and A(g+2) overwrite the buffers stage g-1 read;
+//   every wave retired those ds_reads (lgkmcnt(0) ahead of its last MFMA
+//   group) before it arrived at stage g-1's end barrier, and a wave issues
+//   stage g's loads only after it has left that barrier.
+//   Epilogue privacy: wave w writes its accumulator chunk to
+//   [EPI_OFF + w*EPI_SLICE, +EPI_SLICE) and its own 64 lanes read one 64 B
+//   row each of exactly that slice; no LDS-DMA ever targets the region. A
+//   wave's LDS instructions execute in order and each chunk's writes and
+//   reads are followed by lgkmcnt(0), so write -> read -> next chunk's
+//   write is ordered inside the wave and no other wave is involved: the
+//   epilogue needs no barrier. Waves drift through it independently; one
+//   that finishes early runs on into the next panel's first stage, whose
+//   operands were gated by the last stage's end barrier and whose
+//   prefetches overwrite only buffers every wave finished reading before
+//   that barrier. It then waits at that stage's end barrier, so no wave
+//   gets more than one stage ahead of another.
 //   The filtered kernel finds the next panel with an allowed row before
 //   the stage loop of the current one, so a skipped panel never enters the
 //   stream: buffer rotation and outstanding-load counts do not see it.
@@ -83,32 +102,54 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // tile geometry
 #ifndef KNN_BM
-#define KNN_BM 160
+#define KNN_BM 160  // rows of one row group (one wave's accumulator tile)
 #endif
-#define BM KNN_BM
+#ifndef KNN_RG
+#define KNN_RG 2  // row groups per workgroup
+#endif
+static_assert(KNN_RG == 1 || KNN_RG == 2, "KNN_RG is 1 or 2");
+#define HM KNN_BM           // rows per row group
+#define BM (KNN_RG * HM)    // rows per panel
 #define BN 256
 #define BK 32  // K extent of one pipeline stage
-#define NTHREADS 256
+#define NWAVES (4 * KNN_RG)
+#define NTHREADS (64 * NWAVES)
 #define KCAND 10
-#define MW (BM / 16)
+#define MW (HM / 16)
 
 #define SB_BYTES (BN * BK * 2)  // one query stage: 16 KB
-#define SA_BYTES (BM * BK * 2)  // one corpus stage: 10 KB at BM=160
-#define SMEM_BYTES (2 * SB_BYTES + 3 * SA_BYTES)
+#define SA_BYTES (BM * BK * 2)  // one corpus stage: 20 KB at BM=320
+// epilogue: one [64 cols][16 rows] fp32 block per wave, behind the rings
+#define EPI_SLICE (64 * 16 * 4)
+#define EPI_OFF (2 * SB_BYTES + 3 * SA_BYTES)
+#define EPI_BYTES (NWAVES * EPI_SLICE)
+#define SMEM_BYTES (EPI_OFF + EPI_BYTES)
+// Epilogue privacy (see header): a wave's four ds_write_b128 (offsets
+// nn * 1024, lane part < 1024) cover exactly its slice, its 64 lanes read
+// one 64 B row each of the same slice, and the region holds one slice per
+// wave behind every DMA target.
+static_assert(EPI_SLICE == 4 * (16 * 64),
+              "a wave's four ds_write_b128 (16 cols x 64 B each) fill a slice");
+static_assert(EPI_SLICE == WAVE * 64,
+              "a wave's lanes read one 64 B row each of the same slice");
+static_assert(EPI_OFF >= 2 * SB_BYTES + 3 * SA_BYTES &&
+                  EPI_OFF + NWAVES * EPI_SLICE <= SMEM_BYTES,
+              "one slice per wave, behind every LDS-DMA target");
 
 // LDS-DMA instructions per wave per stage. A stage is BM/16 pieces of 1 KB
-// (16 rows x 64 B); each wave stages A_FULL whole pieces and, when the
-// piece count is 2 mod 4, one half piece (8 rows, lanes 0-31).
+// (16 rows x 64 B); each wave stages A_FULL whole pieces and, when half a
+// wave count of pieces is left over, one half piece (8 rows, lanes 0-31).
 #define A_PIECES (BM / 16)
-#define A_FULL (A_PIECES / 4)
-#define A_HALF (A_PIECES % 4 == 2 ? 1 : 0)
+#define A_FULL (A_PIECES / NWAVES)
+#define A_HALF (A_PIECES % NWAVES == NWAVES / 2 ? 1 : 0)
 #define NA (A_FULL + A_HALF)
-#define NB (BN / 16 / 4)
-static_assert(A_PIECES % 4 == 0 || A_PIECES % 4 == 2,
-              "corpus stage must split evenly over 4 waves");
-// resident workgroups per CU the tile is sized for
-#define KNN_WGS (BM <= 96 ? 3 : 2)
+#define NB (BN / 16 / NWAVES)
+static_assert(A_PIECES % NWAVES == 0 || A_PIECES % NWAVES == NWAVES / 2,
+              "corpus stage must split evenly over the waves");
+// resident workgroups per CU the tile is sized for: 8 waves per CU
+#define KNN_WGS (KNN_RG == 2 ? 1 : 2)
 static_assert(SMEM_BYTES * KNN_WGS <= 160 * 1024, "LDS budget per CU");
+static_assert(SMEM_BYTES <= 128 * 1024, "static LDS limit per workgroup");
 
 namespace knn_mfma_detail {
 
@@ -165,8 +206,10 @@ __device__ __forceinline__ void glds(const char* gbase, unsigned voff,
 }  // namespace knn_mfma_detail
 
 // FILTERED: `allow` is a packed row mask (bit r&31 of word r>>5 set = local
-// row r may be returned); a panel is BM/32 whole words. FILTERED=false
-// never touches `allow`.
+// row r may be returned); a row group is HM/32 whole words and a panel
+// BM/32. FILTERED=false never touches `allow`.
+// cand_* are [gridDim.x * KNN_RG, BN, KCAND]: one list per (block, row
+// group, query column).
 template <bool FILTERED>
 __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
     const unsigned short* __restrict__ db, const unsigned short* __restrict__ qs,
@@ -175,17 +218,21 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
     long long row_base, float* __restrict__ cand_score,
     int* __restrict__ cand_idx, const unsigned int* __restrict__ allow) {
   using namespace knn_mfma_detail;
-  static_assert(!FILTERED || BM % 32 == 0,
-                "filtered kNN needs whole mask words per panel");
+  static_assert(!FILTERED || HM % 32 == 0,
+                "filtered kNN needs whole mask words per row group");
   // One array for all LDS (a second __shared__ object makes hipcc wait
-  // vmcnt(0) ahead of LDS reads): sB[2] at 0, sA[3] behind them.
+  // vmcnt(0) ahead of LDS reads): sB[2] at 0, sA[3] behind them, then the
+  // epilogue slices.
   __shared__ __align__(16) char smem[SMEM_BYTES];
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
-  const int wc = __builtin_amdgcn_readfirstlane(tid / WAVE);  // wave 0..3
+  const int wv = __builtin_amdgcn_readfirstlane(tid / WAVE);  // wave 0..W-1
+  const int wc = wv & 3;   // query quarter: columns wc*64 .. wc*64+63
+  const int rg = wv >> 2;  // row group: panel rows rg*HM .. rg*HM+HM-1
 
-  // per-thread top-K state: this thread owns query column tid.
+  // per-thread top-K state: this thread owns query column tid % BN of row
+  // group rg.
   float tv[KCAND];
   int ti[KCAND];
 #pragma unroll
@@ -217,26 +264,27 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
     const unsigned voff =
         (unsigned)((lane >> 2) * d2 +
                    (((lane & 3) ^ (((lane >> 4) & 1) << 1)) << 4));
-    const char* qbase = (const char*)qs + (long long)(wc * 64) * d2;
+    // wave wv stages query pieces wv*NB .. wv*NB+NB-1 (16 rows each)
+    const char* qbase = (const char*)qs + (long long)(wv * NB * 16) * d2;
 
     auto issue_b = [&](int s, int boff) {
       const char* g = qbase + s * (BK * 2);
 #pragma unroll
       for (int c = 0; c < NB; ++c)
         glds(g + (long long)(c * 16) * d2, voff,
-                smem + boff + (wc * NB + c) * 1024);
+                smem + boff + (wv * NB + c) * 1024);
     };
     auto issue_a = [&](long long prow, int s, int aoff) {
       const char* g = (const char*)db + prow * d2 + s * (BK * 2);
 #pragma unroll
       for (int c = 0; c < A_FULL; ++c)
-        glds(g + (long long)((wc * A_FULL + c) * 16) * d2, voff,
-                    smem + aoff + (wc * A_FULL + c) * 1024);
+        glds(g + (long long)((wv * A_FULL + c) * 16) * d2, voff,
+                    smem + aoff + (wv * A_FULL + c) * 1024);
       if constexpr (A_HALF) {
-        // last two pieces as four 8-row halves, one per wave
+        // last NWAVES/2 pieces as NWAVES 8-row halves, one per wave
         if (lane < 32)
-          glds(g + (long long)(4 * A_FULL * 16 + wc * 8) * d2, voff,
-                      smem + aoff + 4 * A_FULL * 1024 + wc * 512);
+          glds(g + (long long)(NWAVES * A_FULL * 16 + wv * 8) * d2, voff,
+                      smem + aoff + NWAVES * A_FULL * 1024 + wv * 512);
       }
     };
 
@@ -244,13 +292,15 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
     const unsigned foff = (unsigned)swz((lane & 15) * 64 + (lane >> 4) * 16);
     const unsigned lds0 = (unsigned)(unsigned long long)(L_AS char*)smem;
     const unsigned fb = lds0 + wc * (64 * BK * 2) + foff;  // + sB offset
-    const unsigned fa = lds0 + foff;                       // + sA offset
+    const unsigned fa = lds0 + rg * (HM * BK * 2) + foff;  // + sA offset
     // epilogue block [col][16] fp32, 64 B rows, slot ^= (col>>2)&3: the
     // column owner's float4 reads (one row per lane, same slot) spread a
-    // 16-lane group over 16 distinct 16 B positions.
-    const unsigned ew = lds0 + wc * 4096 + (lane & 15) * 64 +
+    // 16-lane group over 16 distinct 16 B positions. Both addresses stay
+    // inside this wave's slice at `eb`.
+    const unsigned eb = lds0 + EPI_OFF + wv * EPI_SLICE;
+    const unsigned ew = eb + (lane & 15) * 64 +
                         (((lane >> 4) ^ ((lane >> 2) & 3)) << 4);
-    const unsigned er = tid * 64 + (((tid >> 2) & 3) << 4);  // slot 0
+    const unsigned er = lane * 64 + (((lane >> 2) & 3) << 4);  // slot 0, + eb
 
     int b_cur = 0, b_nxt = SB_BYTES;
     int a_cur = 2 * SB_BYTES, a_nxt = a_cur + SA_BYTES, a_nn = a_nxt + SA_BYTES;
@@ -268,10 +318,12 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
       const long long nxt = next_live(panel + gridDim.x);
       const long long prow_pf = (nxt < n_panels ? nxt : panel) * BM;
 
-      unsigned int aw[(BM + 31) / 32];
+      // mask words of this wave's row group
+      unsigned int aw[(HM + 31) / 32];
       if constexpr (FILTERED) {
 #pragma unroll
-        for (int h = 0; h < BM / 32; ++h) aw[h] = allow[(prow >> 5) + h];
+        for (int h = 0; h < HM / 32; ++h)
+          aw[h] = allow[((prow + rg * HM) >> 5) + h];
       }
 
       float4v acc[MW][4];
@@ -330,27 +382,25 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
         }
       }
 
-      // ---- epilogue: 16-row chunks through the transposed block in the
-      // query buffer the last stage read (b_nxt after the swap) ----
+      // ---- epilogue: 16-row chunks through this wave's transposed block;
+      // no barrier, the slice is wave-private (see header) ----
       // the asm stores below read MFMA results: cover the MFMA-write ->
       // LDS-read wait states the compiler cannot see into the asm for
       asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-      const unsigned ewb = ew + b_nxt, erb = lds0 + b_nxt;
       static_for<0, MW>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
         static_for<0, 4>([&](auto nn) {
-          ds_write128<decltype(nn)::value * 1024>(ewb,
+          ds_write128<decltype(nn)::value * 1024>(ew,
                                                   acc[m][decltype(nn)::value]);
         });
         wait_lgkm<0>();
-        __builtin_amdgcn_s_barrier();
         float4v v[4];
         static_for<0, 4>([&](auto sl) {
           ds_read128<0>(v[decltype(sl)::value],
-                        erb + (er ^ (unsigned)(decltype(sl)::value << 4)));
+                        eb + (er ^ (unsigned)(decltype(sl)::value << 4)));
         });
         wait_lgkm<0>();
-        const long long grow0 = prow + m * 16;
+        const long long grow0 = prow + rg * HM + m * 16;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
           float s = v[j >> 2][j & 3];
@@ -370,7 +420,6 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
             }
           }
         }
-        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
       });
 
@@ -381,8 +430,8 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
     wait_vm<0>();
   }
 
-  // ---- write candidates ----
-  long long slot = (long long)blockIdx.x * BN + tid;
+  // ---- write candidates: list (block * KNN_RG + rg), column tid % BN ----
+  long long slot = (long long)blockIdx.x * (BN * KNN_RG) + tid;
 #pragma unroll
   for (int i = 0; i < KCAND; ++i) {
     cand_score[slot * KCAND + i] = tv[i];
@@ -503,13 +552,16 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "knn_mfma");
 
   long long n_panels = n / BM;
-  // Persistent-style grid: 1536 = 3 blocks per resident slot at 2
-  // workgroups/CU (and 2 per slot at 3/CU), so every dispatch wave is
-  // full. Each block walks many panels back to back through one stage
-  // stream; its top-k thresholds tighten early and the candidate buffers
-  // and the merge shrink with the grid. Swept at 100M rows (160-row tile):
-  // 7680 61.7 ms, 3072 60.2 ms, 1536 59.4 ms. NORNICDB_KNN_GRID overrides.
-  int max_grid = 1536;
+  // Persistent-style grid: 3 blocks per resident slot (256 CUs x KNN_WGS
+  // workgroups), so every dispatch wave is full: 768 at KNN_RG = 2, 1536
+  // at KNN_RG = 1. Each block walks many panels back to back through one
+  // stage stream; its top-k thresholds tighten early and the candidate
+  // buffers and the merge shrink with the grid. Swept at 100M rows,
+  // KNN_RG = 2: 1536 57.2 ms, 768 56.2, 512 55.8, 256 55.1 (parent kernel
+  // 60.0); end to end 256 and 768 are within each other's spread, so the
+  // default stays at the grid that does not depend on every CU keeping
+  // pace (profiles/README.md). NORNICDB_KNN_GRID overrides.
+  int max_grid = 256 * KNN_WGS * 3;
   if (const char* g = getenv("NORNICDB_KNN_GRID")) max_grid = atoi(g);
   int grid = (int)std::min<long long>(n_panels, max_grid);
   auto stream = at::hip::getCurrentHIPStream().stream();
@@ -517,8 +569,10 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   auto opts_f = db.options().dtype(at::kFloat);
   auto opts_i32 = db.options().dtype(at::kInt);
   auto opts_i64 = db.options().dtype(at::kLong);
-  at::Tensor cand_s = at::empty({grid, BN, KCAND}, opts_f);
-  at::Tensor cand_i = at::empty({grid, BN, KCAND}, opts_i32);
+  // one candidate list per (block, row group, query column)
+  const long long n_lists = (long long)grid * KNN_RG;
+  at::Tensor cand_s = at::empty({n_lists, BN, KCAND}, opts_f);
+  at::Tensor cand_i = at::empty({n_lists, BN, KCAND}, opts_i32);
 
   if (allow_p == nullptr) {
     launch_knn_mfma<false>(grid, stream, db, q, n_panels, d, row_base, cand_s,
@@ -536,11 +590,13 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   at::Tensor out_s = at::empty({BN, k_out}, opts_f);
   at::Tensor out_i = at::empty({BN, k_out}, opts_i64);
   hipLaunchKernelGGL((k_topk_merge_i32<KCAND>), dim3(BN), dim3(256), 0, stream,
-                     cand_s.data_ptr<float>(), cand_i.data_ptr<int>(), grid,
+                     cand_s.data_ptr<float>(), cand_i.data_ptr<int>(), n_lists,
                      BN, k_out, row_base, out_s.data_ptr<float>(),
                      reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()));
   HIP_CHECK_LAST();
   return {out_s, out_i};
 }
 
+// panel height (rows the kernel route consumes at a time) and row groups
 long long knn_bm_value() { return BM; }
+long long knn_rg_value() { return KNN_RG; }

@@ -7,7 +7,8 @@ thread per vector and a <<<1,1>>> top-k). Here:
 - small query batches (Q <= 16): fused HIP kernel `knn_gemv` — wave-per-row
   short8 vector loads, per-lane register top-k, one read of the shard total;
 - large query batches (Q 9..256, k <= 10): fused MFMA score+top-k kernel
-  (96x256 tile, 3 WG/CU, swizzled LDS; csrc/knn_mfma.hip);
+  (320x256 tile: 8 waves as two 160-row groups on one staged query tile,
+  1 WG/CU, pipelined LDS-DMA stages, swizzled LDS; csrc/knn_mfma.hip);
 - CPU: exact fp32 torch reference (also the numerics oracle for GPU tests).
 
 Filtered search: every entry point takes an optional `allow` row mask that
@@ -26,7 +27,9 @@ from . import native_or_none, require_native
 
 
 def _knn_bm() -> int:
-    """Panel row count compiled into the kernel (KNN_BM, default 96)."""
+    """Panel row count compiled into the kernel: KNN_RG row groups of KNN_BM
+    rows, 2 x 160 = 320 by default. Shards shorter than one panel do not
+    take the kernel route; rows past the last full panel are the tail."""
     nat = native_or_none()
     return int(getattr(nat, "KNN_BM", 96)) if nat is not None else 96
 

@@ -32,11 +32,15 @@ setup(
             sources=sources,
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
-                # NORNICDB_KNN_BM overrides the kNN panel-tile rows
-                # (experiment knob; default 96 in knn_mfma.hip)
-                "nvcc": ["-O3", "-std=c++17"] + (
-                    ["-DKNN_BM=" + os.environ["NORNICDB_KNN_BM"]]
-                    if os.environ.get("NORNICDB_KNN_BM") else []),
+                # kNN tile knobs of knn_mfma.hip: NORNICDB_KNN_RG is the
+                # number of 4-wave row groups per workgroup (1 or 2, default
+                # 2: one 8-wave workgroup per CU); NORNICDB_KNN_BM the rows
+                # of one row group (experiment knob; default 160). A panel
+                # is KNN_RG * KNN_BM rows.
+                "nvcc": ["-O3", "-std=c++17"] + [
+                    "-D" + macro + "=" + os.environ["NORNICDB_" + macro]
+                    for macro in ("KNN_BM", "KNN_RG")
+                    if os.environ.get("NORNICDB_" + macro)],
             },
         )
     ],
