@@ -24,6 +24,7 @@ std::tuple<at::Tensor, at::Tensor> ivf_scan_fp8(
 // knn_mfma.hip
 long long knn_bm_value();
 long long knn_rg_value();
+long long knn_stagger_value();
 #define KNN_BM_VALUE knn_bm_value()
 std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
                                             long long row_base, int k_out,
@@ -130,6 +131,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // KNN_BM: rows of one kNN panel; KNN_RG: row groups the panel is made of
   m.attr("KNN_BM") = KNN_BM_VALUE;
   m.attr("KNN_RG") = knn_rg_value();
+  // KNN_STAGGER: 1 when row group 1 runs half a stage behind row group 0
+  m.attr("KNN_STAGGER") = knn_stagger_value();
   m.def("knn_mfma", &knn_mfma,
         "Fused MFMA cosine score + top-k, 256-query batches (bf16 db)",
         py::arg("db"), py::arg("q"), py::arg("row_base") = 0,

@@ -18,6 +18,10 @@
 //     path, 2.67 B at 96 rows, 1.6 B at 160, 0.8 B at 320. With KNN_RG = 2
 //     both row groups read one staged copy of the query stage where two
 //     independent workgroups each staged their own.
+//     KNN_STAGGER = 1 (default, KNN_RG = 2 only): row group 1 runs half
+//     a stage behind row group 0, so that on every SIMD one wave's MFMAs
+//     run beside its partner's loads, waits and epilogue ("Pipeline
+//     ordering, staggered form" below). Same scores and indices.
 //   * one flat stream of BK=32 stages per workgroup: the (panel, k) loops
 //     are flattened, stage g = (panel, 32-wide K slice). Per stage a wave
 //     runs 40 mfma_f32_16x16x32_bf16 (ascending k per accumulator, the
@@ -44,8 +48,9 @@
 //   * corpus loads use the default cache policy: non-temporal (aux = 2)
 //     measured 22 % slower (81.8 vs 67.1 ms at 100M rows, 96-row tile).
 //
-// Pipeline ordering (VM loads retire in order; counts are per wave, W =
-// 4 * KNN_RG waves; numbers for W = 8, in brackets for W = 4):
+// Pipeline ordering, lockstep form (KNN_STAGGER = 0, and KNN_RG = 1). VM
+// loads retire in order; counts are per wave, W = 4 * KNN_RG waves; numbers
+// for W = 8, in brackets for W = 4:
 //   stage g issues  B(g+1)  NB = 2 [4] instructions  -> sB[(g+1)&1]
 //          then     A(g+2)  NA = 3 instructions      -> sA[(g+2)%3]
 //   (NB = 256 query rows / 16 rows per 1 KB piece / W waves; NA = panel/16
@@ -67,6 +72,70 @@
 //   every wave retired those ds_reads (lgkmcnt(0) ahead of its last MFMA
 //   group) before it arrived at stage g-1's end barrier, and a wave issues
 //   stage g's loads only after it has left that barrier.
+//
+// Pipeline ordering, staggered form (KNN_STAGGER = 1 with KNN_RG = 2). Row
+// group 0 (waves 0-3, the leader) and row group 1 (waves 4-7, the
+// follower; wave w and w+4 share a SIMD) run the same stage program half a
+// stage apart, so that one partner's MFMAs run beside the other's DMA
+// issue, fragment reads, waits and epilogue. A stage is two segments, each
+// ended by a workgroup s_barrier:
+//   L(g)  issue the prefetch DMAs; read the 4 B fragments and the first
+//         AH = 5 A fragments of stage g; s_waitcnt lgkmcnt(AH): LDS returns
+//         in order, so the 4 B reads (issued first) are back; s_barrier.
+//   C(g)  the MFMA ladder (10 groups of 4, the other 5 A reads interleaved
+//         behind counted lgkmcnt, the last group behind lgkmcnt(0));
+//         s_waitcnt vmcnt(NA); s_barrier.
+//   Number the barrier intervals t = 0, 1, ... from the prologue's barrier.
+//   The leader runs L(g) in t = 2g and C(g) in t = 2g+1; the follower takes
+//   one extra barrier behind the prologue (it sits out t = 0) and runs L(g)
+//   in t = 2g+1 and C(g) in t = 2g+2. Both run the same loop body; only the
+//   extra barrier and who stages the queries differ.
+//   Staging. Each row group's four waves stage that group's own 160 rows
+//   of the corpus stage: 10 pieces = 2 whole pieces + one 8-row half piece
+//   per wave, NA = 3 as before, into the group's half of sA[.] (offset
+//   rowgroup * 160 * 64 B, the half its own fragments are read from). The
+//   leader's four waves stage the whole query stage, NB = 4 pieces each,
+//   ahead of their A pieces; follower waves issue no query DMA.
+//   Queue at the vmcnt(3) that ends C(g), oldest first:
+//     leader    A(g+1)[3], B(g+1)[4], A(g+2)[3]
+//     follower  A(g+1)[3], A(g+2)[3]
+//   everything older having been retired by C(g-1)'s wait; vmcnt(3) retires
+//   all but A(g+2) in both. The prologue issues A(0), B(0) (leader), A(1)
+//   and waits vmcnt(3): A(0) and B(0) have landed before its barrier.
+//   sA[j], one row group's half (ring of 3, private to the group's waves):
+//     written by the group's A(g+2) DMA, issued in its L(g), j = (g+2)%3;
+//     read by the group's waves in L(g+2) (first 5 fragments) and C(g+2).
+//     Read-after-DMA: each wave's vmcnt(3) at the end of C(g+1) retires its
+//     A(g+2) pieces, the barrier behind it makes that hold for the group's
+//     four waves, and L(g+2) lies behind that barrier.
+//     Write-after-read: the half was last read in the group's C(g-1), whose
+//     ladder ends with lgkmcnt(0) ahead of the barrier that ends C(g-1);
+//     the group's L(g) lies behind that barrier. The other group never
+//     touches this half, so its skew does not enter.
+//   sB[j] (double buffer, shared by both groups):
+//     written by the leader's B(g+1) DMA, issued in its L(g), t = 2g,
+//     j = (g+1)&1; read only in L segments (all 4 B fragments of a stage
+//     are read there and kept in registers through C): by the leader in
+//     L(g+1), t = 2g+2, and by the follower in L(g+1), t = 2g+3.
+//     Read-after-DMA: the leader's vmcnt(3) at the end of C(g), t = 2g+1,
+//     retires B(g+1) ahead of the barrier that ends t = 2g+1; both readers
+//     lie behind that barrier, one and two intervals later.
+//     Write-after-read: sB[(g+1)&1] held stage g-1. Its last reader is the
+//     follower's L(g-1) in t = 2g-1, whose lgkmcnt(AH) retires the B reads
+//     ahead of the barrier that ends t = 2g-1; the leader's L(g) lies behind
+//     that barrier (the leader's own L(g-1) was t = 2g-2).
+//   Barriers per wave over a stream of G stages: 1 (prologue) + 2G + 1 in
+//   both groups: the follower's extra one directly behind the prologue, the
+//   leader's behind its last epilogue, where it closes the interval of the
+//   follower's C(G-1). Panel boundaries add none: the epilogue is barrier-
+//   free and the stage stream runs on, so the leader's epilogue falls into
+//   the interval of the follower's last C of the panel and the follower's
+//   into that of the leader's C of the next panel's first stage. A skipped
+//   panel (filtered kernel) never enters the stream and adds none either;
+//   next_live() reads the whole panel's mask words in every wave, so both
+//   groups walk the same panel sequence. A workgroup without a live panel
+//   takes no barrier at all (block-uniform branch).
+//
 //   Epilogue privacy: wave w writes its accumulator chunk to
 //   [EPI_OFF + w*EPI_SLICE, +EPI_SLICE) and its own 64 lanes read one 64 B
 //   row each of exactly that slice; no LDS-DMA ever targets the region. A
@@ -78,13 +147,17 @@
 //   operands were gated by the last stage's end barrier and whose
 //   prefetches overwrite only buffers every wave finished reading before
 //   that barrier. It then waits at that stage's end barrier, so no wave
-//   gets more than one stage ahead of another.
+//   gets more than one stage ahead of another (staggered: at the barrier
+//   that ends the first stage's L segment, so the two groups keep their
+//   half-stage distance and no wave gets a segment ahead within a group).
 //   The filtered kernel finds the next panel with an allowed row before
 //   the stage loop of the current one, so a skipped panel never enters the
 //   stream: buffer rotation and outstanding-load counts do not see it.
 //   At the end of the stream the prefetches are still issued (from the
 //   current panel's rows, never used) to keep the counts uniform, and a
-//   vmcnt(0) ahead of the candidate write-out retires them.
+//   vmcnt(0) ahead of the candidate write-out retires them. They target
+//   ring buffers only, under the same write-after-read argument as any
+//   other stage's, and the LDS is released when the last wave has ended.
 //
 // Replaces the reference's cublasSgemv + single-thread top-k scan
 // (reference: pkg/gpu/cuda/cuda_kernels.cu:340-480).
@@ -108,6 +181,12 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define KNN_RG 2  // row groups per workgroup
 #endif
 static_assert(KNN_RG == 1 || KNN_RG == 2, "KNN_RG is 1 or 2");
+#ifndef KNN_STAGGER
+#define KNN_STAGGER 1  // row group 1 runs half a stage behind row group 0
+#endif
+static_assert(KNN_STAGGER == 0 || KNN_STAGGER == 1, "KNN_STAGGER is 0 or 1");
+// the stagger needs two row groups in one workgroup; KNN_RG = 1 ignores it
+#define KNN_STAG (KNN_STAGGER == 1 && KNN_RG == 2)
 #define HM KNN_BM           // rows per row group
 #define BM (KNN_RG * HM)    // rows per panel
 #define BN 256
@@ -136,16 +215,30 @@ static_assert(EPI_OFF >= 2 * SB_BYTES + 3 * SA_BYTES &&
                   EPI_OFF + NWAVES * EPI_SLICE <= SMEM_BYTES,
               "one slice per wave, behind every LDS-DMA target");
 
-// LDS-DMA instructions per wave per stage. A stage is BM/16 pieces of 1 KB
-// (16 rows x 64 B); each wave stages A_FULL whole pieces and, when half a
-// wave count of pieces is left over, one half piece (8 rows, lanes 0-31).
-#define A_PIECES (BM / 16)
-#define A_FULL (A_PIECES / NWAVES)
-#define A_HALF (A_PIECES % NWAVES == NWAVES / 2 ? 1 : 0)
+// LDS-DMA instructions per wave per stage. A staging set is SWAVES waves
+// that share one staging job: all NWAVES waves stage the whole panel and
+// the query tile, or, staggered, each row group's four waves stage that
+// group's A_ROWS = HM rows and row group 0's four waves the query tile. A
+// set's corpus stage is A_ROWS/16 pieces of 1 KB (16 rows x 64 B); each
+// wave stages A_FULL whole pieces and, when half a wave count of pieces is
+// left over, one half piece (8 rows, lanes 0-31).
+#if KNN_STAG
+#define SWAVES 4
+#define A_ROWS HM
+#else
+#define SWAVES NWAVES
+#define A_ROWS BM
+#endif
+#define A_PIECES (A_ROWS / 16)
+#define A_FULL (A_PIECES / SWAVES)
+#define A_HALF (A_PIECES % SWAVES == SWAVES / 2 ? 1 : 0)
 #define NA (A_FULL + A_HALF)
-#define NB (BN / 16 / NWAVES)
-static_assert(A_PIECES % NWAVES == 0 || A_PIECES % NWAVES == NWAVES / 2,
+#define NB (BN / 16 / SWAVES)
+static_assert(A_PIECES % SWAVES == 0 || A_PIECES % SWAVES == SWAVES / 2,
               "corpus stage must split evenly over the waves");
+static_assert(!KNN_STAG || (HM * BK * 2) % 512 == 0 &&
+                               ((HM * BK * 2) & 256) == 0,
+              "a row group's staging base keeps the swizzle bit clear");
 // resident workgroups per CU the tile is sized for: 8 waves per CU
 #define KNN_WGS (KNN_RG == 2 ? 1 : 2)
 static_assert(SMEM_BYTES * KNN_WGS <= 160 * 1024, "LDS budget per CU");
@@ -264,27 +357,36 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
     const unsigned voff =
         (unsigned)((lane >> 2) * d2 +
                    (((lane & 3) ^ (((lane >> 4) & 1) << 1)) << 4));
-    // wave wv stages query pieces wv*NB .. wv*NB+NB-1 (16 rows each)
-    const char* qbase = (const char*)qs + (long long)(wv * NB * 16) * d2;
+    // Staging set (see SWAVES): wave sw of its set. Staggered, a row group
+    // stages its own rows, arow0 .. arow0+HM-1 of the panel, which sit
+    // arow0 * 64 B into a corpus buffer, and only row group 0 stages
+    // queries; otherwise the one set is the workgroup.
+    constexpr bool STAG = KNN_STAG;
+    const int sw = STAG ? wc : wv;
+    const int arow0 = STAG ? rg * HM : 0;
+    // wave sw stages query pieces sw*NB .. sw*NB+NB-1 (16 rows each)
+    const char* qbase = (const char*)qs + (long long)(sw * NB * 16) * d2;
 
     auto issue_b = [&](int s, int boff) {
       const char* g = qbase + s * (BK * 2);
 #pragma unroll
       for (int c = 0; c < NB; ++c)
         glds(g + (long long)(c * 16) * d2, voff,
-                smem + boff + (wv * NB + c) * 1024);
+                smem + boff + (sw * NB + c) * 1024);
     };
     auto issue_a = [&](long long prow, int s, int aoff) {
-      const char* g = (const char*)db + prow * d2 + s * (BK * 2);
+      const char* g =
+          (const char*)db + (prow + arow0) * d2 + s * (BK * 2);
+      char* l = smem + aoff + arow0 * (BK * 2);
 #pragma unroll
       for (int c = 0; c < A_FULL; ++c)
-        glds(g + (long long)((wv * A_FULL + c) * 16) * d2, voff,
-                    smem + aoff + (wv * A_FULL + c) * 1024);
+        glds(g + (long long)((sw * A_FULL + c) * 16) * d2, voff,
+                    l + (sw * A_FULL + c) * 1024);
       if constexpr (A_HALF) {
-        // last NWAVES/2 pieces as NWAVES 8-row halves, one per wave
+        // last SWAVES/2 pieces as SWAVES 8-row halves, one per wave
         if (lane < 32)
-          glds(g + (long long)(NWAVES * A_FULL * 16 + wv * 8) * d2, voff,
-                      smem + aoff + NWAVES * A_FULL * 1024 + wv * 512);
+          glds(g + (long long)(SWAVES * A_FULL * 16 + sw * 8) * d2, voff,
+                      l + SWAVES * A_FULL * 1024 + sw * 512);
       }
     };
 
@@ -307,10 +409,16 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
 
     // prologue: A(0), B(0), A(1); gate the first two
     issue_a(panel * BM, 0, a_cur);
-    issue_b(0, b_cur);
+    if (!STAG || rg == 0) issue_b(0, b_cur);
     issue_a(panel * BM, 1, a_nxt);
     wait_vm<NA>();
     __builtin_amdgcn_s_barrier();
+    if constexpr (STAG) {
+      // the follower sits out interval 0: from here on it runs one
+      // barrier interval (half a stage) behind the leader
+      if (rg == 1) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    }
 
     for (;;) {
       const long long prow = panel * BM;
@@ -334,7 +442,7 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
 
       for (int s = 0; s < nstage; ++s) {
         // ---- prefetch: queries of the next stage, corpus two ahead ----
-        issue_b(s + 1 == nstage ? 0 : s + 1, b_nxt);
+        if (!STAG || rg == 0) issue_b(s + 1 == nstage ? 0 : s + 1, b_nxt);
         {
           const bool wrap = s + 2 >= nstage;
           issue_a(wrap ? prow_pf : prow, wrap ? s + 2 - nstage : s + 2, a_nn);
@@ -356,6 +464,14 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
         static_for<0, AH>([&](auto m) {
           ds_read128<decltype(m)::value * 1024>(afr[decltype(m)::value], ra);
         });
+        if constexpr (STAG) {
+          // end of the load segment: the B fragments (the first four reads,
+          // LDS returns in order) are back, so the query buffer is free for
+          // the leader's next DMA; the AH A reads stay in flight
+          wait_lgkm<AH>();
+          __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_sched_barrier(0);
+        }
         __builtin_amdgcn_s_setprio(1);
         static_for<0, MW>([&](auto mc) {
           constexpr int m = decltype(mc)::value;
@@ -425,6 +541,12 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
 
       if (nxt >= n_panels) break;
       panel = nxt;
+    }
+    if constexpr (STAG) {
+      // the leader's last epilogue ran beside the follower's last compute
+      // segment; this barrier closes that interval, so that every wave
+      // has taken 2 + 2 * stages barriers
+      if (rg == 0) __builtin_amdgcn_s_barrier();
     }
     // end of stream: retire the unused tail prefetches before the LDS goes
     wait_vm<0>();
@@ -552,16 +674,19 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "knn_mfma");
 
   long long n_panels = n / BM;
-  // Persistent-style grid: 3 blocks per resident slot (256 CUs x KNN_WGS
-  // workgroups), so every dispatch wave is full: 768 at KNN_RG = 2, 1536
-  // at KNN_RG = 1. Each block walks many panels back to back through one
-  // stage stream; its top-k thresholds tighten early and the candidate
-  // buffers and the merge shrink with the grid. Swept at 100M rows,
-  // KNN_RG = 2: 1536 57.2 ms, 768 56.2, 512 55.8, 256 55.1 (parent kernel
-  // 60.0); end to end 256 and 768 are within each other's spread, so the
-  // default stays at the grid that does not depend on every CU keeping
-  // pace (profiles/README.md). NORNICDB_KNN_GRID overrides.
-  int max_grid = 256 * KNN_WGS * 3;
+  // Persistent-style grid. Lockstep builds: 3 blocks per resident slot (256
+  // CUs x KNN_WGS workgroups), so every dispatch wave is full: 768 at
+  // KNN_RG = 2, 1536 at KNN_RG = 1. Each block walks many panels back to
+  // back through one stage stream; its top-k thresholds tighten early and
+  // the candidate buffers and the merge shrink with the grid. Swept at 100M
+  // rows, KNN_RG = 2, lockstep: 1536 57.2 ms, 768 56.2, 512 55.8, 256 55.1;
+  // end to end 256 and 768 were within each other's spread there. The
+  // staggered build gains only with long-lived blocks (kernel, same box:
+  // 768 55.5-56.0 ms against 55.7-56.0 lockstep, 512 55.0-55.2 against
+  // 55.5-55.6, 256 54.2-54.6 against 55.0-55.3) and one block per CU wins
+  // end to end by more than the runs' spread in two sessions, so its
+  // default is 256 (profiles/README.md). NORNICDB_KNN_GRID overrides.
+  int max_grid = KNN_STAG ? 256 : 256 * KNN_WGS * 3;
   if (const char* g = getenv("NORNICDB_KNN_GRID")) max_grid = atoi(g);
   int grid = (int)std::min<long long>(n_panels, max_grid);
   auto stream = at::hip::getCurrentHIPStream().stream();
@@ -600,3 +725,5 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
 // panel height (rows the kernel route consumes at a time) and row groups
 long long knn_bm_value() { return BM; }
 long long knn_rg_value() { return KNN_RG; }
+// 1 when the built kernel staggers its row groups (KNN_RG = 2 only)
+long long knn_stagger_value() { return KNN_STAG ? 1 : 0; }

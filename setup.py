@@ -36,10 +36,12 @@ setup(
                 # number of 4-wave row groups per workgroup (1 or 2, default
                 # 2: one 8-wave workgroup per CU); NORNICDB_KNN_BM the rows
                 # of one row group (experiment knob; default 160). A panel
-                # is KNN_RG * KNN_BM rows.
+                # is KNN_RG * KNN_BM rows. NORNICDB_KNN_STAGGER (0 or 1, with
+                # KNN_RG = 2 only) runs row group 1 half a stage behind row
+                # group 0.
                 "nvcc": ["-O3", "-std=c++17"] + [
                     "-D" + macro + "=" + os.environ["NORNICDB_" + macro]
-                    for macro in ("KNN_BM", "KNN_RG")
+                    for macro in ("KNN_BM", "KNN_RG", "KNN_STAGGER")
                     if os.environ.get("NORNICDB_" + macro)],
             },
         )
