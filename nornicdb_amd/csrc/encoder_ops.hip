@@ -6,20 +6,13 @@
 //   - k_add_layernorm      : y = LN(a + b) * gamma + beta   (bf16, fp32 stats)
 //   - k_bias_gelu          : y = gelu_erf(x + bias)          (bf16)
 //   - k_mean_pool_l2norm   : masked mean over S + L2 norm    (bf16 -> fp32)
-//   - k_flash_attn_nc      : non-causal flash attention, head_dim 64,
-//                            16x16x32 MFMA QK^T and PV, online softmax,
-//                            V transposed at stage time in LDS.
+// (The attention kernel lives in flash_attn.hip.)
 // All memory-bound kernels use short8 (16 B/lane) vector loads per the
 // CDNA4 guide (G13).
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#define G_AS __attribute__((address_space(1)))
-#define L_AS __attribute__((address_space(3)))
 
 // ---------------------------------------------------------------------------
 // y = LayerNorm(a + b) * gamma + beta. Rows = tokens, D % 8 == 0, D <= 8192.
@@ -148,204 +141,6 @@ __global__ void k_mean_pool_l2norm(const unsigned short* __restrict__ x,
     out[(long long)b * d + c] = s_acc[c] * inv;
 }
 
-// ---------------------------------------------------------------------------
-// Non-causal flash attention forward, head_dim 64, bf16, no mask
-// (full attention; padded batches fall back to torch sdpa in python).
-//
-// q,k,v: [B, H, S, 64] bf16 contiguous. out: same.
-// Block: 256 thr = 4 waves; one (b, h, 64-query tile) per block.
-// Wave w owns q rows [w*16, w*16+16). K-tile loop of 64 keys:
-//   K staged linear (global_load_lds, tile is contiguous 8 KB),
-//   V staged TRANSPOSED via registers (VT[d][k], 2-way-bank-free),
-//   QK^T: 2x mfma 16x16x32 per 16-key subtile (B-frag direct from K rows),
-//   online softmax in C-fragment registers (16-lane group reduces),
-//   P -> LDS (bf16) -> A-frags; PV: mfma with B-frags from VT.
-// ---------------------------------------------------------------------------
-#define FA_D 64
-#define FA_KT 64
-#define FA_QT 64
-#define FA_PSTRIDE 64   // measured: 64 beats 72 by 15% (208 vs 181 TF; scripts/attn_pad.hip sweep)
-#define FA_VSTRIDE 80   // measured best with gather-V staging (232 vs 226 TF at 72)
-
-__global__ __launch_bounds__(256, 2) void k_flash_attn_nc(
-    const unsigned short* __restrict__ Q, const unsigned short* __restrict__ K,
-    const unsigned short* __restrict__ V, unsigned short* __restrict__ O,
-    int n_heads, int s, float scale,
-    long long q_bs, long long q_ss,   // Q batch/seq strides (elements)
-    long long k_bs, long long k_ss,
-    long long v_bs, long long v_ss) {
-  // Layout: Q/K/V are [B, S, H, 64] views with arbitrary batch/seq strides
-  // (head stride == 64, last dim contiguous) so the qkv projection output
-  // feeds in with ZERO transposes; O is contiguous [B, S, H, 64].
-  __shared__ unsigned short sK[FA_KT * FA_D];          // 8 KB, linear
-  __shared__ unsigned short sVT[FA_D * FA_VSTRIDE];    // 9 KB, transposed
-  __shared__ unsigned short sP[4][16 * FA_PSTRIDE];    // 4 x 2.25 KB
-
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int b = blockIdx.x / n_heads;
-  const int h = blockIdx.x % n_heads;
-  const int q0 = blockIdx.y * FA_QT;
-  const long long hoff = (long long)h * FA_D;
-
-  const int lq = lane & 15;           // row-in-16 for A-frags / col for C
-  const int lk8 = (lane >> 4) * 8;    // k-offset for A/B frags
-
-  // ---- load Q fragments for this wave's 16 rows (held for whole kernel) ----
-  // A-frag for QK^T: lane holds Q[q=lq][d = lk8 + ks*32 .. +8], ks = 0,1
-  bf16x8 qf[2];
-  {
-    const unsigned short* qp =
-        Q + b * q_bs + (long long)(q0 + wid * 16 + lq) * q_ss + hoff;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-      qf[ks] = (bf16x8)(*reinterpret_cast<const short8v*>(qp + ks * 32 + lk8));
-  }
-
-  // online softmax state: per lane, 4 q-rows (r = 0..3 of its 16-lane group)
-  float m_run[4], l_run[4];
-  float4v acc[4];  // output [16q][64d]: 4 d-subtiles x 4 regs
-#pragma unroll
-  for (int r = 0; r < 4; ++r) { m_run[r] = -1e30f; l_run[r] = 0.f; }
-#pragma unroll
-  for (int nn = 0; nn < 4; ++nn) acc[nn] = {0.f, 0.f, 0.f, 0.f};
-
-  const float log2e = 1.44269504f;
-
-  for (int k0 = 0; k0 < s; k0 += FA_KT) {
-    // ---- stage K tile: 64 rows x 128 B (strided source, linear LDS) ----
-    {
-      const unsigned short* kp = K + b * k_bs + hoff;
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        int chunk = wid * 2 + it;
-        int byte_off = chunk * 1024 + lane * 16;
-        int r = byte_off / (FA_D * 2);
-        int cb = byte_off % (FA_D * 2);
-        const G_AS unsigned int* gp = (const G_AS unsigned int*)(
-            (const char*)(kp + (long long)(k0 + r) * k_ss) + cb);
-        L_AS unsigned int* lp = (L_AS unsigned int*)((char*)sK + chunk * 1024);
-        __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
-      }
-    }
-    // ---- stage V transposed: gather 8 consecutive k at fixed d, ONE
-    // b128 LDS write per octet. The strided global reads hit L1/L2 (the
-    // V tile is 8 KB); swapping the cost off the LDS write port was
-    // +5% within-probe on top of the stride fix (scripts/attn_pad.hip:
-    // 216 -> 227 TF, refchecked).
-    {
-      const unsigned short* vp = V + b * v_bs + hoff;
-      int dd = threadIdx.x & 63;          // d fixed per thread
-      int k8 = (threadIdx.x >> 6) * 16;   // two k-octets per thread
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        int kk = k8 + half * 8;
-        short8v o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          o[j] = (short)vp[(long long)(k0 + kk + j) * v_ss + dd];
-        *reinterpret_cast<short8v*>(sVT + dd * FA_VSTRIDE + kk) = o;
-      }
-    }
-    __syncthreads();
-
-    // ---- QK^T: 4 k-subtiles of 16 ----
-    float4v sfrag[4];
-#pragma unroll
-    for (int nn = 0; nn < 4; ++nn) {
-      float4v c4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        // B-frag: lane holds K[k = nn*16 + lq][d = lk8 + ks*32 .. +8]
-        bf16x8 bf = (bf16x8)(*reinterpret_cast<const short8v*>(
-            sK + (nn * 16 + lq) * FA_D + ks * 32 + lk8));
-        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[ks], bf, c4, 0, 0, 0);
-      }
-      sfrag[nn] = c4;
-    }
-
-    // ---- online softmax ----
-    // sfrag[nn][r] = S[q = (lane>>4)*4 + r][k = nn*16 + lq] * (pending scale)
-    float pmax[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float mx = -1e30f;
-#pragma unroll
-      for (int nn = 0; nn < 4; ++nn) mx = fmaxf(mx, sfrag[nn][r]);
-      // reduce across the 16 lanes of this group
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1)
-        mx = fmaxf(mx, __shfl_xor(mx, off, WAVE));
-      pmax[r] = mx * scale;
-    }
-    float rescale[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float mn = fmaxf(m_run[r], pmax[r]);
-      rescale[r] = exp2f((m_run[r] - mn) * log2e);
-      m_run[r] = mn;
-      l_run[r] *= rescale[r];
-    }
-    // p = exp(s*scale - m); accumulate l; write P to LDS bf16
-    float lsum[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int nn = 0; nn < 4; ++nn) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float p = exp2f((sfrag[nn][r] * scale - m_run[r]) * log2e);
-        lsum[r] += p;
-        sP[wid][((lane >> 4) * 4 + r) * FA_PSTRIDE + nn * 16 + lq] =
-            f32_to_bf16_bits(p);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float ls = lsum[r];
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1)
-        ls += __shfl_xor(ls, off, WAVE);
-      l_run[r] += ls;
-    }
-    // rescale existing output acc
-#pragma unroll
-    for (int nn = 0; nn < 4; ++nn)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[nn][r] *= rescale[r];
-
-    __syncthreads();  // P visible to own wave only, but VT/K rewrite below
-
-    // ---- PV: A = P [16q x 64k] from sP, B = V^T from sVT ----
-#pragma unroll
-    for (int nn = 0; nn < 4; ++nn) {       // d-subtile
-      float4v c4 = acc[nn];
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {     // k-dim halves of 32
-        bf16x8 af = (bf16x8)(*reinterpret_cast<const short8v*>(
-            sP[wid] + lq * FA_PSTRIDE + ks * 32 + lk8));
-        bf16x8 bf = (bf16x8)(*reinterpret_cast<const short8v*>(
-            sVT + (nn * 16 + lq) * FA_VSTRIDE + ks * 32 + lk8));
-        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, c4, 0, 0, 0);
-      }
-      acc[nn] = c4;
-    }
-    __syncthreads();
-  }
-
-  // ---- epilogue: normalize by l, write O [B,S,H,64] contiguous ----
-  const long long o_ss = (long long)n_heads * FA_D;
-  const long long obase =
-      ((long long)b * s + q0 + wid * 16) * o_ss + hoff;
-#pragma unroll
-  for (int nn = 0; nn < 4; ++nn) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int row = (lane >> 4) * 4 + r;
-      float v = acc[nn][r] / fmaxf(l_run[r], 1e-20f);
-      O[obase + row * o_ss + nn * 16 + lq] = f32_to_bf16_bits(v);
-    }
-  }
-}
-
 // ===========================================================================
 // Host wrappers
 // ===========================================================================
@@ -419,30 +214,3 @@ at::Tensor mean_pool_l2norm(at::Tensor x, c10::optional<at::Tensor> mask) {
   return out;
 }
 
-at::Tensor flash_attn_nc(at::Tensor q, at::Tensor k, at::Tensor v) {
-  // q,k,v: [B, S, H, 64] bf16 VIEWS — head stride must be 64 and the last
-  // dim contiguous; batch/seq strides are free (so qkv.unbind(2) feeds in
-  // without any transpose/copy). Returns contiguous [B, S, H, 64].
-  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.scalar_type() == at::kBFloat16,
-              "flash_attn_nc: q [B,S,H,D] bf16");
-  int B = (int)q.size(0), S = (int)q.size(1), H = (int)q.size(2),
-      D = (int)q.size(3);
-  TORCH_CHECK(D == 64, "flash_attn_nc supports head_dim 64");
-  TORCH_CHECK(S % 64 == 0, "flash_attn_nc needs S % 64 == 0");
-  for (auto* t : {&q, &k, &v}) {
-    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == D,
-                "flash_attn_nc: head stride must be D, last dim contiguous");
-  }
-  at::Tensor o = at::empty({B, S, H, D}, q.options());
-  float scale = 1.0f / sqrtf((float)D);
-  dim3 grid(B * H, S / 64);
-  hipLaunchKernelGGL(k_flash_attn_nc, grid, dim3(256), 0, enc_stream(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)k.data_ptr(),
-                     (const unsigned short*)v.data_ptr(),
-                     (unsigned short*)o.data_ptr(), H, S, scale,
-                     q.stride(0), q.stride(1), k.stride(0), k.stride(1),
-                     v.stride(0), v.stride(1));
-  HIP_CHECK_LAST();
-  return o;
-}

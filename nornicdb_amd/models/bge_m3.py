@@ -91,9 +91,11 @@ class _EncoderLayer(nn.Module):
             from nornicdb_amd.ops import encoder as eops
             from nornicdb_amd.ops.gemm import ACT_GELU, linear_act
 
-            # all four GEMMs are the hand-written MFMA kernel, with bias
-            # (and the FFN GELU) fused into the epilogue — zero Tensile
-            # kernels on the serve path.
+            # all four GEMMs go through linear_act, whose default dispatch
+            # (NORNICDB_GEMM=auto) routes them to hipBLASLt, with bias+GELU
+            # as a fused HIP kernel behind ffn_in; NORNICDB_GEMM=hand
+            # selects the hand-written MFMA kernels (bias and GELU in the
+            # epilogue) instead.
             x = eops.add_layernorm(
                 x, linear_act(a, self.attn_out.weight, self.attn_out.bias),
                 self.ln1.weight, self.ln1.bias, self.ln1.eps)

@@ -1,6 +1,9 @@
-// Standalone A/B: FA_PSTRIDE/FA_VSTRIDE padding variants for
-// k_flash_attn_nc (copy of the production kernel parameterized by
-// strides; refcheck vs itself at default).
+// Standalone A/B: FA_PSTRIDE/FA_VSTRIDE padding variants of the FORMER
+// k_flash_attn_nc (16x16x32 MFMA, P through LDS, 64 query rows per
+// workgroup; a copy parameterized by strides, refcheck vs itself at
+// default). That kernel was replaced by csrc/flash_attn.hip, which has
+// neither stride; kept as the source of the padding figures in
+// profiles/README.md.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
