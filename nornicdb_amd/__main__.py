@@ -27,6 +27,9 @@ def _open(args, cfg):
     if getattr(cfg, "search_quant", ""):
         # SearchService reads the env at index construction
         os.environ.setdefault("NORNICDB_SEARCH_QUANT", cfg.search_quant)
+    if getattr(cfg, "qdrant_device", "cpu") != "cpu":
+        # the HTTP server reads the env when it builds its Qdrant registry
+        os.environ.setdefault("NORNICDB_QDRANT_DEVICE", cfg.qdrant_device)
 
     provider = "mock" if cfg.embedder == "mock" else cfg.embedder
     try:

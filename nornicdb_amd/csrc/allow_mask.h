@@ -22,3 +22,22 @@ static inline const unsigned int* check_allow_mask(const at::Tensor& allow,
               allow.numel(), " words, need ", (n + 31) / 32);
   return reinterpret_cast<const unsigned int*>(allow.data_ptr<int>());
 }
+
+// Per-row score bias of the bf16 kNN kernels: fp32 [n], indexed like the
+// mask by local row (before row_base). The score that enters the top-k is
+// dot(q, row) + row_bias[row]. Values must be finite and far above the
+// kernels' -1e30 list sentinel; nothing tests for that. Validates
+// `row_bias` against the n rows the kernel will score and returns its
+// device pointer.
+static inline const float* check_row_bias(const at::Tensor& row_bias,
+                                          const at::Tensor& db, long long n,
+                                          const char* who) {
+  TORCH_CHECK(row_bias.is_cuda() && row_bias.scalar_type() == at::kFloat &&
+                  row_bias.dim() == 1 && row_bias.is_contiguous(),
+              who, ": row_bias must be a contiguous 1D fp32 CUDA tensor");
+  TORCH_CHECK(row_bias.device() == db.device(), who,
+              ": row_bias must be on the same device as db");
+  TORCH_CHECK(row_bias.numel() == n, who, ": row_bias has ", row_bias.numel(),
+              " entries, need ", n);
+  return row_bias.data_ptr<float>();
+}

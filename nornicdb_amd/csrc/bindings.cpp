@@ -6,7 +6,8 @@ void l2_normalize_(at::Tensor x);
 void fill_random_unit_(at::Tensor x, long long row_base, long long seed);
 std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
                                             long long row_base, int k_out,
-                                            c10::optional<at::Tensor> allow);
+                                            c10::optional<at::Tensor> allow,
+                                            c10::optional<at::Tensor> row_bias);
 std::tuple<at::Tensor, at::Tensor> ivf_scan(
     at::Tensor db, at::Tensor q, at::Tensor probes, at::Tensor list_off,
     at::Tensor list_rows, long long tail_start, long long max_len,
@@ -28,7 +29,9 @@ long long knn_stagger_value();
 #define KNN_BM_VALUE knn_bm_value()
 std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
                                             long long row_base, int k_out,
-                                            c10::optional<at::Tensor> allow);
+                                            c10::optional<at::Tensor> allow,
+                                            c10::optional<at::Tensor> row_bias,
+                                            int q_count);
 
 // gemm.hip
 at::Tensor gemm_nt(at::Tensor a, at::Tensor w, c10::optional<at::Tensor> bias,
@@ -103,9 +106,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("row_base") = 0, py::arg("seed") = 0x6e6f726eLL);
   m.def("knn_gemv", &knn_gemv,
         "Fused cosine score + top-k for <=16 queries (bf16 db); allow = "
-        "optional packed int32 row mask (bit r&31 of word r>>5)",
+        "optional packed int32 row mask (bit r&31 of word r>>5); row_bias = "
+        "optional fp32 [N] added to each row's score",
         py::arg("db"), py::arg("q"), py::arg("row_base") = 0,
-        py::arg("k_out") = 10, py::arg("allow") = c10::nullopt);
+        py::arg("k_out") = 10, py::arg("allow") = c10::nullopt,
+        py::arg("row_bias") = c10::nullopt);
   m.def("ivf_scan", &ivf_scan,
         "IVF probe-list scan: fused gather + cosine score + top-k (k <= 64) "
         "over the probed inverted lists and the unclustered tail (bf16 db)",
@@ -134,9 +139,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // KNN_STAGGER: 1 when row group 1 runs half a stage behind row group 0
   m.attr("KNN_STAGGER") = knn_stagger_value();
   m.def("knn_mfma", &knn_mfma,
-        "Fused MFMA cosine score + top-k, 256-query batches (bf16 db)",
+        "Fused MFMA cosine score + top-k, 256-query batches (bf16 db); "
+        "row_bias = optional fp32 [N] added to each row's score; q_count = "
+        "real queries among the 256 rows of q (with row_bias the padding "
+        "columns are not scored; their output rows are undefined)",
         py::arg("db"), py::arg("q"), py::arg("row_base") = 0,
-        py::arg("k_out") = 10, py::arg("allow") = c10::nullopt);
+        py::arg("k_out") = 10, py::arg("allow") = c10::nullopt,
+        py::arg("row_bias") = c10::nullopt, py::arg("q_count") = 256);
   m.def("gemm_nt", &gemm_nt,
         "C = A[M,K] @ W[N,K]^T + bias (+GELU), bf16 MFMA 256x256 8-phase",
         py::arg("a"), py::arg("w"), py::arg("bias") = c10::nullopt,

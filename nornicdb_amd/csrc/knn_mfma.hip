@@ -159,6 +159,42 @@
 //   ring buffers only, under the same write-after-read argument as any
 //   other stage's, and the LDS is released when the last wave has ended.
 //
+// Row bias (BIASED): the score that enters the top-k is dot + row_bias[r],
+// r the local row (before row_base), added in the epilogue where a thread
+// takes v[j>>2][j&3] for row grow0 + j: one fp32 add behind the finished
+// dot product. All 64 lanes of a wave look at the same 16 rows of a chunk,
+// so the 16 biases are wave-uniform and are fetched with scalar loads
+// (plain C++ on a wave-uniform address: one s_load_dwordx16 per chunk, the
+// add takes the SGPR as an operand; no VGPR, no VM-queue entry). Chunk 0's
+// are fetched at the panel's start, beside the filtered kernel's mask
+// words; chunk m+1's during chunk m, into the other of two 16-SGPR buffers
+// (behind chunk m's LDS round trip rather than ahead of it, so that the
+// load runs under chunk m's insertion pass instead of in front of a
+// lgkmcnt(0)). Why this is safe in this pipeline:
+//   * vmcnt is untouched: the loads are SMEM, the wait_vm<NA> accounting of
+//     the stage stream sees nothing new, and no prefetch is drained.
+//   * lgkmcnt: SMEM and LDS share the counter and SMEM may return out of
+//     order. With u scalar loads outstanding at a counted wait_lgkm<N>, at
+//     least issued_lds + u - N operations have completed, of which at most
+//     u are scalar, so at least issued_lds - N LDS operations have: the
+//     wait guarantees what it guaranteed, it can only take longer (chunk
+//     0's load during the first stage; the mask words already live with
+//     this). Their data is needed only in the epilogue, behind lgkmcnt(0).
+//   * first use: chunk m+1's load is issued behind chunk m's second
+//     lgkmcnt(0); chunk m+1's own two lgkmcnt(0) waits retire it ahead of
+//     chunk m+1's first add, and chunk m reads the other buffer. The
+//     compiler counts the load itself as well and puts its own lgkmcnt(0)
+//     ahead of the first add.
+//   * padding columns: a zero query column scores the bare bias, so with
+//     fewer than BN real queries the padding columns' lists are closed at
+//     the start (threshold 3e38, q_count argument); unbiased they score 0
+//     everywhere and stop inserting by themselves.
+//   * bounds: the last element read is row_bias[prow + rg*HM + HM - 1] with
+//     prow + BM <= n_panels * BM = the length the wrapper checked. The
+//     end-of-stream prefetch of an unused panel touches no bias.
+// Biases must be finite and far above the -1e30 list sentinel; the kernel
+// does not test for that.
+//
 // Replaces the reference's cublasSgemv + single-thread top-k scan
 // (reference: pkg/gpu/cuda/cuda_kernels.cu:340-480).
 
@@ -301,15 +337,20 @@ __device__ __forceinline__ void glds(const char* gbase, unsigned voff,
 // FILTERED: `allow` is a packed row mask (bit r&31 of word r>>5 set = local
 // row r may be returned); a row group is HM/32 whole words and a panel
 // BM/32. FILTERED=false never touches `allow`.
+// BIASED: the score that enters the top-k is dot(q, row) + row_bias[r] for
+// local row r, one fp32 add in the epilogue (see "Row bias" in the header).
+// BIASED=false never touches `row_bias`.
 // cand_* are [gridDim.x * KNN_RG, BN, KCAND]: one list per (block, row
 // group, query column).
-template <bool FILTERED>
+template <bool FILTERED, bool BIASED>
 __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
     const unsigned short* __restrict__ db, const unsigned short* __restrict__ qs,
     long long n_panels,  // number of full BM-row panels
     int d,               // inner dim, % 64 == 0
     long long row_base, float* __restrict__ cand_score,
-    int* __restrict__ cand_idx, const unsigned int* __restrict__ allow) {
+    int* __restrict__ cand_idx, const unsigned int* __restrict__ allow,
+    const float* __restrict__ row_bias,
+    int q_count) {  // real queries; columns from q_count up are padding
   using namespace knn_mfma_detail;
   static_assert(!FILTERED || HM % 32 == 0,
                 "filtered kNN needs whole mask words per row group");
@@ -330,6 +371,16 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
   int ti[KCAND];
 #pragma unroll
   for (int i = 0; i < KCAND; ++i) { tv[i] = -1e30f; ti[i] = -1; }
+  if constexpr (BIASED) {
+    // A padding column (zero query) scores the bare bias: distinct values
+    // that would keep inserting like a real query's, where an unbiased
+    // padding column scores 0 everywhere and stops after KCAND rows. Its
+    // list is closed instead; the caller drops these columns.
+    if (tid % BN >= q_count) {
+#pragma unroll
+      for (int i = 0; i < KCAND; ++i) tv[i] = 3e38f;
+    }
+  }
 
   const int d2 = d * 2;       // row stride in bytes
   const int nstage = d / BK;  // stages per panel, even and >= 2
@@ -433,6 +484,15 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
         for (int h = 0; h < HM / 32; ++h)
           aw[h] = allow[((prow + rg * HM) >> 5) + h];
       }
+      // biases of this wave's row group, one 16-row chunk at a time, wave-
+      // uniform (scalar loads): chunk 0 here, chunk m+1 in chunk m's epilogue
+      const float* bias_rg = nullptr;
+      float bz[2][16];
+      if constexpr (BIASED) {
+        bias_rg = row_bias + prow + rg * HM;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) bz[0][j] = bias_rg[j];
+      }
 
       float4v acc[MW][4];
 #pragma unroll
@@ -516,10 +576,28 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
                         eb + (er ^ (unsigned)(decltype(sl)::value << 4)));
         });
         wait_lgkm<0>();
+        if constexpr (BIASED && m + 1 < MW) {
+          // Next chunk's biases, behind this chunk's LDS round trip: the
+          // load is in flight under the insertion pass below, and the next
+          // chunk's first lgkmcnt(0) retires it ahead of its first use.
+          // (Ahead of the ds_writes it would sit in front of that wait and
+          // the wave would stall on it in every chunk.)
+          // The empty asm reads one of THIS chunk's biases. hipcc does not
+          // see the asm waits above and owes that load a lgkmcnt(0) of its
+          // own ahead of the first use; SMEM returns out of order, so placed
+          // behind the new load that wait would drain the new load too. The
+          // read puts it here, where it is free.
+          asm volatile("" ::"s"(bz[m & 1][0]));
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int j = 0; j < 16; ++j)
+            bz[(m + 1) & 1][j] = bias_rg[(m + 1) * 16 + j];
+        }
         const long long grow0 = prow + rg * HM + m * 16;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
           float s = v[j >> 2][j & 3];
+          if constexpr (BIASED) s += bz[m & 1][j];
           bool ok = s > tv[KCAND - 1];
           if constexpr (FILTERED)
             ok = ok && ((aw[m >> 1] >> ((m & 1) * 16 + j)) & 1u);
@@ -642,20 +720,24 @@ __global__ void k_topk_merge_i32(const float* __restrict__ cand_score,
 // host wrapper: full-panel part of the shard only (n_panels * BM rows).
 // The python side handles the tail rows and q-padding to 256.
 // ---------------------------------------------------------------------------
-template <bool FILTERED>
+template <bool FILTERED, bool BIASED>
 static void launch_knn_mfma(int grid, hipStream_t stream, const at::Tensor& db,
                             const at::Tensor& q, long long n_panels, int d,
                             long long row_base, at::Tensor& cand_s,
-                            at::Tensor& cand_i, const unsigned int* allow_p) {
-  hipLaunchKernelGGL((k_knn_mfma<FILTERED>), dim3(grid), dim3(NTHREADS),
+                            at::Tensor& cand_i, const unsigned int* allow_p,
+                            const float* bias_p, int q_count) {
+  hipLaunchKernelGGL((k_knn_mfma<FILTERED, BIASED>), dim3(grid), dim3(NTHREADS),
                      0, stream, (const unsigned short*)db.data_ptr(),
                      (const unsigned short*)q.data_ptr(), n_panels, d, row_base,
-                     cand_s.data_ptr<float>(), cand_i.data_ptr<int>(), allow_p);
+                     cand_s.data_ptr<float>(), cand_i.data_ptr<int>(), allow_p,
+                     bias_p, q_count);
 }
 
 std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
                                             long long row_base, int k_out,
-                                            c10::optional<at::Tensor> allow) {
+                                            c10::optional<at::Tensor> allow,
+                                            c10::optional<at::Tensor> row_bias,
+                                            int q_count) {
   TORCH_CHECK(db.is_cuda() && db.dim() == 2 && db.is_contiguous() &&
                   db.scalar_type() == at::kBFloat16,
               "knn_mfma: db must be contiguous 2D bf16 CUDA");
@@ -670,8 +752,13 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   TORCH_CHECK(n % BM == 0, "knn_mfma needs N % ", BM, " == 0 (python pads/tails)");
   TORCH_CHECK(n < (1LL << 31), "shard too large for int32 local rows");
   TORCH_CHECK(k_out >= 1 && k_out <= KCAND);
+  TORCH_CHECK(q_count >= 1 && q_count <= BN, "knn_mfma: q_count must be 1..",
+              BN);
   const unsigned int* allow_p = nullptr;
   if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "knn_mfma");
+  const float* bias_p = nullptr;
+  if (row_bias.has_value())
+    bias_p = check_row_bias(*row_bias, db, n, "knn_mfma");
 
   long long n_panels = n / BM;
   // Persistent-style grid. Lockstep builds: 3 blocks per resident slot (256
@@ -699,17 +786,18 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
   at::Tensor cand_s = at::empty({n_lists, BN, KCAND}, opts_f);
   at::Tensor cand_i = at::empty({n_lists, BN, KCAND}, opts_i32);
 
-  if (allow_p == nullptr) {
-    launch_knn_mfma<false>(grid, stream, db, q, n_panels, d, row_base, cand_s,
-                           cand_i, allow_p);
-  } else {
+  auto launch = bias_p ? launch_knn_mfma<false, true>
+                       : launch_knn_mfma<false, false>;
+  if (allow_p != nullptr) {
 #if KNN_BM % 32 == 0
-    launch_knn_mfma<true>(grid, stream, db, q, n_panels, d, row_base, cand_s,
-                          cand_i, allow_p);
+    launch = bias_p ? launch_knn_mfma<true, true>
+                    : launch_knn_mfma<true, false>;
 #else
     TORCH_CHECK(false, "knn_mfma: filtered search needs KNN_BM % 32 == 0");
 #endif
   }
+  launch(grid, stream, db, q, n_panels, d, row_base, cand_s, cand_i, allow_p,
+         bias_p, q_count);
   HIP_CHECK_LAST();
 
   at::Tensor out_s = at::empty({BN, k_out}, opts_f);

@@ -134,17 +134,26 @@ __global__ void k_fill_random_unit_bf16(unsigned short* __restrict__ x,
 // loading it, so a selective filter saves HBM traffic in proportion. All
 // 16 lanes of a group share the row and take the same branch; the
 // __shfl_xor offsets (< 16) never leave the group.
+//
+// BIASED: the score that enters the top-k is dot(q, row) + row_bias[row],
+// row_bias fp32 [n] indexed like the mask (local row, before row_base). The
+// group's bias load is issued ahead of the row's loads (its own cache line,
+// in flight with the row's data, as sa[row] in k_ivf_scan_q8) and added
+// once, in fp32, after the 16-lane butterfly has completed the dot product.
+// Biases must be finite and far above the -1e30 list sentinel; the kernel
+// does not test for that. BIASED=false never touches `row_bias`.
 // ---------------------------------------------------------------------------
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 
-template <int QMAX, int K, bool FILTERED>
+template <int QMAX, int K, bool FILTERED, bool BIASED>
 __global__ void k_knn_gemv_bf16(const unsigned short* __restrict__ db,
                                 const unsigned short* __restrict__ qs,
                                 long long n, int d, int q_count,
                                 long long row_base,
                                 float* __restrict__ cand_score,
                                 long long* __restrict__ cand_idx,
-                                const unsigned int* __restrict__ allow) {
+                                const unsigned int* __restrict__ allow,
+                                const float* __restrict__ row_bias) {
   extern __shared__ unsigned short s_q[];  // [q_count][d]
   const int lane = threadIdx.x & (WAVE - 1);
   const int grp = lane >> 4;        // 4 row-groups per wave
@@ -175,6 +184,8 @@ __global__ void k_knn_gemv_bf16(const unsigned short* __restrict__ db,
     if constexpr (FILTERED) {
       if (!((allow[row >> 5] >> (row & 31)) & 1u)) continue;
     }
+    float rb = 0.0f;
+    if constexpr (BIASED) rb = row_bias[row];
     const unsigned short* rp = db + row * d + (long long)gl * 8;
     float acc[QMAX];
 #pragma unroll
@@ -213,6 +224,7 @@ __global__ void k_knn_gemv_bf16(const unsigned short* __restrict__ db,
 #pragma unroll
       for (int q = 1; q < QMAX; ++q)
         if (gl == q) s = acc[q];
+      if constexpr (BIASED) s += rb;
       if (s > tv[K - 1]) {
         float cs = s; long long ci = row_base + row;
 #pragma unroll
@@ -743,7 +755,8 @@ constexpr int KNN_K = 16;
 
 std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
                                             long long row_base, int k_out,
-                                            c10::optional<at::Tensor> allow) {
+                                            c10::optional<at::Tensor> allow,
+                                            c10::optional<at::Tensor> row_bias) {
   TORCH_CHECK(db.is_cuda() && db.dim() == 2 && db.is_contiguous() &&
                   db.scalar_type() == at::kBFloat16,
               "knn_gemv: db must be contiguous 2D bf16 CUDA");
@@ -759,6 +772,9 @@ std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
   TORCH_CHECK(k_out >= 1 && k_out <= KNN_K, "k_out must be <= ", KNN_K);
   const unsigned int* allow_p = nullptr;
   if (allow.has_value()) allow_p = check_allow_mask(*allow, db, n, "knn_gemv");
+  const float* bias_p = nullptr;
+  if (row_bias.has_value())
+    bias_p = check_row_bias(*row_bias, db, n, "knn_gemv");
 
   int cap = 1280;
   if (const char* g = getenv("NORNICDB_GEMV_BLOCKS")) cap = atoi(g);
@@ -773,13 +789,16 @@ std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
   size_t lds = (size_t)qc * d * sizeof(unsigned short);
   TORCH_CHECK(lds <= 64 * 1024, "query LDS tile too large");
 
-  auto launch = allow_p ? k_knn_gemv_bf16<16, KNN_K, true>
-                        : k_knn_gemv_bf16<16, KNN_K, false>;
+  auto launch =
+      bias_p ? (allow_p ? k_knn_gemv_bf16<16, KNN_K, true, true>
+                        : k_knn_gemv_bf16<16, KNN_K, false, true>)
+             : (allow_p ? k_knn_gemv_bf16<16, KNN_K, true, false>
+                        : k_knn_gemv_bf16<16, KNN_K, false, false>);
   hipLaunchKernelGGL(launch, dim3(blocks), dim3(256),
                      lds, cur_stream(), (const unsigned short*)db.data_ptr(),
                      (const unsigned short*)q.data_ptr(), n, d, qc, row_base,
                      cand_s.data_ptr<float>(), reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()),
-                     allow_p);
+                     allow_p, bias_p);
   HIP_CHECK_LAST();
 
   at::Tensor out_s = at::empty({qc, k_out}, opts_f);

@@ -355,6 +355,43 @@ register("point.withinbbox", lambda p, lo, hi: None if p is None else
          (lo.x <= p.x <= hi.x and lo.y <= p.y <= hi.y))
 
 
+# ---- vector similarity (reference functions_eval_math.go:679-713) ----
+def _vec_pair(a, b):
+    """Two equal-length numeric lists as floats, or None."""
+    if not isinstance(a, (list, tuple)) or not isinstance(b, (list, tuple)):
+        return None
+    if len(a) != len(b):
+        return None
+    try:
+        return [float(_num(x)) for x in a], [float(_num(x)) for x in b]
+    except CypherRuntimeError:
+        return None
+
+
+def _vector_similarity_cosine(a, b):
+    p = _vec_pair(a, b)
+    if p is None:
+        return None
+    x, y = p
+    nx = math.sqrt(sum(v * v for v in x))
+    ny = math.sqrt(sum(v * v for v in y))
+    if nx == 0.0 or ny == 0.0:
+        return 0.0
+    return sum(u * v for u, v in zip(x, y)) / (nx * ny)
+
+
+def _vector_similarity_euclidean(a, b):
+    p = _vec_pair(a, b)
+    if p is None:
+        return None
+    x, y = p
+    return 1.0 / (1.0 + math.sqrt(sum((u - v) ** 2 for u, v in zip(x, y))))
+
+
+register("vector.similarity.cosine", _vector_similarity_cosine)
+register("vector.similarity.euclidean", _vector_similarity_euclidean)
+
+
 # Neo4j math semantics: out-of-domain returns NaN (not an error)
 register("sqrt", lambda x: None if x is None else (
     float("nan") if x < 0 else math.sqrt(_num(x))))

@@ -17,6 +17,12 @@ the kernels test before a score can enter the top-k (see pack_allow_mask).
 Scores are inner products — callers are expected to store L2-normalized
 vectors for cosine semantics (same contract as the reference,
 pkg/gpu/gpu.go normalized EmbeddingIndex).
+
+Row bias: knn_search and knn_search_exact take an optional fp32 `row_bias`
+[N]; the score of row r is then q.x_r + row_bias[r] on every route (one fp32
+add behind the finished dot product, fused into both bf16 kernels). With
+row_bias = -|x_r|^2 / 2 the ranking is the Euclidean one; that is how
+EmbeddingIndex(metric="euclidean") searches.
 """
 
 from typing import Optional, Tuple
@@ -105,9 +111,12 @@ def _pad_unfilled(s, i):
 def knn_search_exact(
     db: torch.Tensor, q: torch.Tensor, k: int, row_base: int = 0,
     allow: Optional[torch.Tensor] = None,
+    row_bias: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """fp32 exact reference: returns (scores [Q,k] fp32, indices [Q,k] int64)."""
     scores = q.float() @ db.float().T
+    if row_bias is not None:
+        scores = scores + row_bias.float()
     ok = None if allow is None else _mask_rows(allow, 0, db.shape[0])
     return _masked_topk(scores, ok, k, row_base)
 
@@ -115,15 +124,26 @@ def knn_search_exact(
 def _knn_gemm_chunked(
     db: torch.Tensor, q: torch.Tensor, k: int, row_base: int,
     chunk_rows: int = 4 << 20, allow: Optional[torch.Tensor] = None,
+    row_bias: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Tiled GEMM + top-k. Avoids materializing the full [N, Q] score matrix."""
+    """Tiled GEMM + top-k. Avoids materializing the full [N, Q] score matrix.
+
+    With a row bias the product is taken in fp32, in chunks small enough for
+    an fp32 copy: a bf16 GEMM rounds its output to 8 bits, and q.x + bias
+    cancels (a Euclidean bias is -|x|^2/2 against q.x of the same size)."""
     n = db.shape[0]
     qf = q.to(db.dtype)
+    if row_bias is not None:
+        chunk_rows = min(chunk_rows, 1 << 18)
+        qf = q.float()
     best_s = None
     best_i = None
     for start in range(0, n, chunk_rows):
         stop = min(start + chunk_rows, n)
-        scores = (qf @ db[start:stop].T).float()  # [Q, chunk]
+        if row_bias is None:
+            scores = (qf @ db[start:stop].T).float()  # [Q, chunk]
+        else:
+            scores = qf @ db[start:stop].float().T + row_bias[start:stop]
         kk = min(k, stop - start)
         ok = None if allow is None else _mask_rows(allow, start, stop)
         s, i = _masked_topk(scores, ok, kk, row_base + start)
@@ -137,9 +157,24 @@ def _knn_gemm_chunked(
     return best_s, best_i
 
 
+def _check_row_bias(row_bias: torch.Tensor, db: torch.Tensor) -> torch.Tensor:
+    """Caller's bias -> contiguous fp32 [N] on db's device, or ValueError."""
+    if db.dtype not in (torch.bfloat16, torch.float32, torch.float16):
+        raise ValueError(
+            "row_bias is supported on bf16/float corpora only, not "
+            f"{db.dtype}: metrics on quantised corpora are not implemented")
+    if row_bias.dim() != 1 or row_bias.shape[0] != db.shape[0]:
+        raise ValueError(
+            f"row_bias must be [N] = [{db.shape[0]}], got {tuple(row_bias.shape)}")
+    if row_bias.device != db.device:
+        raise ValueError("row_bias must live on db's device")
+    return row_bias.float().contiguous()
+
+
 def knn_search(
     db: torch.Tensor, q: torch.Tensor, k: int, row_base: int = 0,
     allow: Optional[torch.Tensor] = None,
+    row_bias: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k inner-product search of q (Q x D) against db (N x D).
 
@@ -151,21 +186,30 @@ def knn_search(
     a packed int32 mask (pack_allow_mask) on db's device. With m allowed
     rows the first min(k, m) slots hold the allowed top scores in
     descending order; every remaining slot is (score -inf, index -1).
+
+    row_bias: optional fp32 [N] on db's device, indexed like the mask by
+    local row (before row_base). Scores become q.x + row_bias[row] on every
+    route; `allow` and `row_bias` combine. Values must be finite and far
+    above -1e30, the kernels' empty-slot sentinel (not tested). Raises
+    ValueError on a quantised (fp8) corpus.
     """
     assert db.dim() == 2 and q.dim() == 2 and db.shape[1] == q.shape[1]
     k = min(k, db.shape[0])
+    if row_bias is not None:
+        row_bias = _check_row_bias(row_bias, db)
     if allow is None:
-        return _knn_dispatch(db, q, k, row_base, None)
+        return _knn_dispatch(db, q, k, row_base, None, row_bias)
     assert allow.device == db.device, "allow mask must live on db's device"
     if db.is_cuda:
         allow = _mask_words(allow, db.shape[0])
-    return _pad_unfilled(*_knn_dispatch(db, q, k, row_base, allow))
+    return _pad_unfilled(*_knn_dispatch(db, q, k, row_base, allow, row_bias))
 
 
-def _knn_dispatch(db, q, k, row_base, allow):
-    """Q/k/dtype routing; allow is None or (on GPU) packed mask words."""
+def _knn_dispatch(db, q, k, row_base, allow, row_bias=None):
+    """Q/k/dtype routing; allow is None or (on GPU) packed mask words,
+    row_bias None or contiguous fp32 [N] (never with an fp8 corpus)."""
     if not db.is_cuda:
-        return knn_search_exact(db, q, k, row_base, allow)
+        return knn_search_exact(db, q, k, row_base, allow, row_bias)
     if db.dtype == torch.float8_e4m3fn:
         nat = native_or_none()
         if nat is None:
@@ -194,7 +238,7 @@ def _knn_dispatch(db, q, k, row_base, allow):
         and db.shape[1] % 128 == 0
     ):
         qq = q.to(torch.bfloat16).contiguous()
-        return nat.knn_gemv(db.contiguous(), qq, row_base, k, allow)
+        return nat.knn_gemv(db.contiguous(), qq, row_base, k, allow, row_bias)
     if (
         k <= 10
         and db.dtype == torch.bfloat16
@@ -202,12 +246,13 @@ def _knn_dispatch(db, q, k, row_base, allow):
         and db.shape[0] >= _knn_bm()
     ):
         if q.shape[0] <= 256:
-            return _knn_mfma(nat, db, q, k, row_base, allow)
+            return _knn_mfma(nat, db, q, k, row_base, allow, row_bias)
         # large query batches (multi-GPU all-gather): chunk through the
         # fused kernel 256 queries at a time
         ss, ii = [], []
         for s in range(0, q.shape[0], 256):
-            cs, ci = _knn_mfma(nat, db, q[s:s + 256], k, row_base, allow)
+            cs, ci = _knn_mfma(nat, db, q[s:s + 256], k, row_base, allow,
+                               row_bias)
             ss.append(cs)
             ii.append(ci)
         return torch.cat(ss, 0), torch.cat(ii, 0)
@@ -220,8 +265,9 @@ def _knn_dispatch(db, q, k, row_base, allow):
         # Q 9..16 with k 11..16: MFMA path capped at k<=10, gemv still wins
         # over the chunked-GEMM fallback at these batch sizes
         qq = q.to(torch.bfloat16).contiguous()
-        return nat.knn_gemv(db.contiguous(), qq, row_base, k, allow)
-    return _knn_gemm_chunked(db, q, k, row_base, allow=allow)
+        return nat.knn_gemv(db.contiguous(), qq, row_base, k, allow, row_bias)
+    return _knn_gemm_chunked(db, q, k, row_base, allow=allow,
+                             row_bias=row_bias)
 
 
 def quantize_fp8(db: torch.Tensor) -> torch.Tensor:
@@ -244,6 +290,7 @@ def quantize_int8(db: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 def knn_search_int8(
     db: torch.Tensor, sa: torch.Tensor, q: torch.Tensor, k: int,
     row_base: int = 0, allow: Optional[torch.Tensor] = None,
+    row_bias: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k over a symmetric int8 corpus (per-row scales sa).
 
@@ -251,8 +298,13 @@ def knn_search_int8(
     panels and the tail score identical values. i32 dots are exact in
     fp32 up to d*127^2 < 2^24 (d <= 1024).
 
-    allow: optional row filter, same forms and contract as knn_search."""
+    allow: optional row filter, same forms and contract as knn_search.
+    row_bias: not supported on a quantised corpus; anything but None raises
+    ValueError."""
     assert db.dtype == torch.int8 and db.dim() == 2
+    if row_bias is not None:
+        raise ValueError("row_bias is not supported on an int8 corpus: "
+                         "metrics on quantised corpora are not implemented")
     k = min(k, db.shape[0])
     if allow is None:
         return _knn_int8_dispatch(db, sa, q, k, row_base, None)
@@ -379,7 +431,7 @@ def _knn_fp8_chunked(db, q, k, row_base, chunk_rows: int = 4 << 20,
     return best_s, best_i
 
 
-def _knn_mfma(nat, db, q, k, row_base, allow=None):
+def _knn_mfma(nat, db, q, k, row_base, allow=None, row_bias=None):
     """Fused MFMA score+topk over full BM-row panels + torch-scored tail."""
     qn = q.shape[0]
     qq = q.to(torch.bfloat16)
@@ -391,11 +443,19 @@ def _knn_mfma(nat, db, q, k, row_base, allow=None):
     n = db.shape[0]
     bm = _knn_bm()
     n_main = (n // bm) * bm
-    s, i = nat.knn_mfma(db.narrow(0, 0, n_main), qq, row_base, k, allow)
+    s, i = nat.knn_mfma(
+        db.narrow(0, 0, n_main), qq, row_base, k, allow,
+        None if row_bias is None else row_bias.narrow(0, 0, n_main), qn)
     s, i = s[:qn], i[:qn]
     if n_main < n:
         tail = db.narrow(0, n_main, n - n_main)
-        ts = (qq[:qn] @ tail.T).float()
+        if row_bias is None:
+            ts = (qq[:qn] @ tail.T).float()
+        else:
+            # fp32 product: the bf16 GEMM's rounded output would not survive
+            # the cancellation against the bias
+            ts = qq[:qn].float() @ tail.float().T + \
+                row_bias.narrow(0, n_main, n - n_main)
         kk = min(k, n - n_main)
         ok = None if allow is None else _mask_rows(allow, n_main, n)
         bs, bi = _masked_topk(ts, ok, kk, row_base + n_main)

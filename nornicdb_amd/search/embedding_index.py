@@ -4,6 +4,13 @@ Replaces reference pkg/gpu/gpu.go EmbeddingIndex (:1224: dirty-tracking
 auto-sync, ScoreSubset :1554) with a single CDNA4 path: vectors live in a
 bf16 torch tensor on the MI355X (fp32 numpy on CPU test runs), scored by
 the fused HIP kNN kernels (ops.knn_search). No multi-backend probing.
+
+Metric (reference pkg/qdrantgrpc/vector_index_cache.go, pkg/math/vector/
+similarity.go): `cosine` L2-normalises rows and queries and scores inner
+products; `dot` stores and scores vectors as given; `euclidean` stores
+vectors as given beside a per-row bias -|x|^2/2, so that the kernels' inner
+product plus bias ranks by distance (argmax q.x - |x|^2/2 = argmin |q-x|),
+then re-scores the k hits exactly and returns 1 / (1 + distance).
 """
 
 from __future__ import annotations
@@ -14,11 +21,19 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .vectorspace import COSINE, EUCLIDEAN, normalize_metric
+
 
 class EmbeddingIndex:
     def __init__(self, dims: int, device: Optional[str] = None,
-                 capacity: int = 1024, quant: Optional[str] = None):
+                 capacity: int = 1024, quant: Optional[str] = None,
+                 metric: str = COSINE):
         self.dims = dims
+        self.metric = normalize_metric(metric)
+        if quant is not None and self.metric != COSINE:
+            raise ValueError(
+                f"metric {self.metric!r} needs an unquantised index: "
+                f"quant={quant!r} corpora score cosine only")
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
@@ -42,6 +57,10 @@ class EmbeddingIndex:
         self._buf = torch.zeros(capacity, dims, device=self.device, dtype=self.dtype)
         self._scales = (torch.zeros(capacity, device=self.device)
                         if quant == "int8" else None)
+        # euclidean: -|row|^2 / 2 of the stored (rounded) row, fp32, kept in
+        # step with _buf: written wherever a row is written
+        self._bias = (torch.zeros(capacity, device=self.device)
+                      if self.metric == EUCLIDEAN else None)
         self._n = 0
         self._ids: List[str] = []
         self._id2slot: Dict[str, int] = {}
@@ -72,6 +91,10 @@ class EmbeddingIndex:
             ns = torch.zeros(new_cap, device=self.device)
             ns[:self._n] = self._scales[:self._n]
             self._scales = ns
+        if self._bias is not None:
+            nbias = torch.zeros(new_cap, device=self.device)
+            nbias[:self._n] = self._bias[:self._n]
+            self._bias = nbias
         nl = np.zeros(new_cap, dtype=bool)
         nl[:self._n] = self._live[:self._n]
         self._live = nl
@@ -81,32 +104,41 @@ class EmbeddingIndex:
         t = t.float()
         return t / torch.linalg.vector_norm(t, dim=-1, keepdim=True).clamp_min(1e-12)
 
+    def _prep(self, t: torch.Tensor) -> torch.Tensor:
+        """Rows or queries as the metric scores them: L2-normalised for
+        cosine, as given for dot and euclidean (fp32 either way)."""
+        return self._normalize(t) if self.metric == COSINE else t.float()
+
     def _store_rows(self, m: torch.Tensor):
-        """normalized fp32 rows -> (rows in storage dtype, scales|None)"""
+        """prepared fp32 rows -> (rows in storage dtype, scales|None)"""
         if self.quant == "int8":
             from ..ops.knn import quantize_int8
             return quantize_int8(m)
         return m.to(self.dtype), None
 
+    def _write_row(self, slot: int, row: torch.Tensor, scale) -> None:
+        """The one place a stored row changes: row, scale and bias together."""
+        self._buf[slot] = row
+        if scale is not None:
+            self._scales[slot] = scale
+        if self._bias is not None:
+            self._bias[slot] = -0.5 * row.float().square().sum()
+
     def add(self, id_: str, vec) -> None:
         with self._lock:
             v = torch.as_tensor(np.asarray(vec, dtype=np.float32),
                                 device=self.device)
-            v, sc = self._store_rows(self._normalize(v.reshape(1, -1)))
+            v, sc = self._store_rows(self._prep(v.reshape(1, -1)))
             slot = self._id2slot.get(id_)
             if slot is not None:
-                self._buf[slot] = v[0]
-                if sc is not None:
-                    self._scales[slot] = sc[0]
+                self._write_row(slot, v[0], None if sc is None else sc[0])
                 self._dead.discard(slot)
                 self._set_live(slot, True)
                 for hook in self._overwrite_hooks:
                     hook(slot)
                 return
             self._grow(self._n + 1)
-            self._buf[self._n] = v[0]
-            if sc is not None:
-                self._scales[self._n] = sc[0]
+            self._write_row(self._n, v[0], None if sc is None else sc[0])
             self._ids.append(id_)
             self._id2slot[id_] = self._n
             self._set_live(self._n, True)
@@ -115,22 +147,19 @@ class EmbeddingIndex:
     def add_batch(self, ids: Sequence[str], mat) -> None:
         with self._lock:
             m = torch.as_tensor(np.asarray(mat, dtype=np.float32), device=self.device)
-            m, sc = self._store_rows(self._normalize(m))
+            m, sc = self._store_rows(self._prep(m))
             self._grow(self._n + len(ids))
             for i, id_ in enumerate(ids):
                 slot = self._id2slot.get(id_)
                 if slot is not None:
-                    self._buf[slot] = m[i]
-                    if sc is not None:
-                        self._scales[slot] = sc[i]
+                    self._write_row(slot, m[i], None if sc is None else sc[i])
                     self._dead.discard(slot)
                     self._set_live(slot, True)
                     for hook in self._overwrite_hooks:
                         hook(slot)
                 else:
-                    self._buf[self._n] = m[i]
-                    if sc is not None:
-                        self._scales[self._n] = sc[i]
+                    self._write_row(self._n, m[i],
+                                    None if sc is None else sc[i])
                     self._ids.append(id_)
                     self._id2slot[id_] = self._n
                     self._set_live(self._n, True)
@@ -184,10 +213,28 @@ class EmbeddingIndex:
                                        self._scales[:self._n], q, kk)
             return knn_search_int8(self._buf[:self._n],
                                    self._scales[:self._n], q, kk, allow=mask)
+        if self._bias is not None:
+            s, i = knn_search(self._buf[:self._n], q.to(self.dtype), kk,
+                              allow=mask, row_bias=self._bias[:self._n])
+            return self._rescore_euclidean(q, i)
         if mask is None:
             return knn_search(self._buf[:self._n], q.to(self.dtype), kk)
         return knn_search(self._buf[:self._n], q.to(self.dtype), kk,
                           allow=mask)
+
+    def _rescore_euclidean(self, q: torch.Tensor, i: torch.Tensor):
+        """Exact scores for the slots a biased search returned: fp32
+        |q - row| against the stored rows, re-sorted ascending, returned as
+        1 / (1 + distance) (descending). The kernel's q.x - |x|^2/2 only
+        ranks: turning it back into a distance, |q|^2 - 2s, cancels for near
+        duplicates. Unfilled slots (index -1) stay last with score -inf."""
+        rows = self._buf[i.clamp_min(0)].float()           # [Q, k, D]
+        dist = torch.linalg.vector_norm(q.float()[:, None, :] - rows, dim=-1)
+        dist = dist.masked_fill(i < 0, float("inf"))
+        dist, order = torch.sort(dist, dim=-1, stable=True)
+        i = torch.gather(i, -1, order)
+        score = (1.0 / (1.0 + dist)).masked_fill(i < 0, float("-inf"))
+        return score, i
 
     def search(self, query, k: int,
                allow_ids: Optional[Iterable[str]] = None
@@ -201,7 +248,7 @@ class EmbeddingIndex:
                 return []
             q = torch.as_tensor(np.asarray(query, dtype=np.float32),
                                 device=self.device).reshape(1, -1)
-            q = self._normalize(q)
+            q = self._prep(q)
             s, i = self._knn(q, k, allow_ids)
             out = []
             for score, slot in zip(s[0].tolist(), i[0].tolist()):
@@ -220,7 +267,7 @@ class EmbeddingIndex:
                 return [[] for _ in range(len(queries))]
             q = torch.as_tensor(np.asarray(queries, dtype=np.float32),
                                 device=self.device)
-            q = self._normalize(q)
+            q = self._prep(q)
             s, i = self._knn(q, k, allow_ids)
             outs = []
             for r in range(q.shape[0]):
@@ -242,12 +289,16 @@ class EmbeddingIndex:
                 return []
             q = torch.as_tensor(np.asarray(query, dtype=np.float32),
                                 device=self.device).reshape(-1)
-            q = self._normalize(q.reshape(1, -1))[0]
+            q = self._prep(q.reshape(1, -1))[0]
             sl = torch.as_tensor(slots, device=self.device)
             sub = self._buf[sl].float()
             if self._scales is not None:
                 sub = sub * self._scales[sl, None]
-            scores = (sub @ q.float()).tolist()
+            if self.metric == EUCLIDEAN:
+                dist = torch.linalg.vector_norm(sub - q.float(), dim=-1)
+                scores = (1.0 / (1.0 + dist)).tolist()
+            else:
+                scores = (sub @ q.float()).tolist()
             kept = [i for i in ids if i in self._id2slot]
             return sorted(zip(kept, scores), key=lambda kv: -kv[1])
 

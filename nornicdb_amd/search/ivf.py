@@ -31,8 +31,14 @@ REBUILD_RATIO = 0.2   # same drift ratio as ClusterIndex.needs_recluster
 
 class IVFIndex:
     def __init__(self, emb: EmbeddingIndex, nprobe: int = 8):
+        if getattr(emb, "metric", "cosine") != "cosine":
+            # the scan kernels and the centroid routing score inner products
+            # of normalised vectors only
+            raise ValueError(
+                f"IVFIndex needs a cosine EmbeddingIndex, got metric "
+                f"{emb.metric!r}")
         self.emb = emb
-        self._lock = emb._lock          # one lock for vectors and lists
+        self._lock = emb._lock         # one lock for vectors and lists
         self._nprobe = nprobe
         self._lists: Optional[IVFLists] = None
         self._stale: set = set()

@@ -14,6 +14,26 @@ COSINE = "cosine"
 DOT = "dot"
 EUCLIDEAN = "euclidean"
 
+_METRIC_ALIASES = {
+    "cosine": COSINE,
+    "dot": DOT,
+    "euclid": EUCLIDEAN,
+    "euclidean": EUCLIDEAN,
+    "l2": EUCLIDEAN,
+}
+
+
+def normalize_metric(name: str) -> str:
+    """Canonical metric for a user-facing name (case-insensitive): cosine;
+    dot; euclid / euclidean / l2. Anything else raises ValueError. This is
+    the name EmbeddingIndex(metric=...) scores with; Registry keeps storing
+    whatever distance string it is given."""
+    key = name.strip().lower() if isinstance(name, str) else None
+    if key not in _METRIC_ALIASES:
+        raise ValueError(f"unknown vector metric {name!r}: expected one of "
+                         f"{sorted(_METRIC_ALIASES)}")
+    return _METRIC_ALIASES[key]
+
 
 @dataclass
 class VectorSpace:

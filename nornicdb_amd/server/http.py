@@ -865,7 +865,11 @@ def create_app(mgr: DatabaseManager, auth=None, version: str = "0.1.0") -> FastA
         _qeng = mgr.get().engine
     except Exception:
         _qeng = None
-    app.state.qdrant = QdrantRegistry(engine=_qeng)
+    # NORNICDB_QDRANT_DEVICE = cpu (default) | cuda | auto: where the
+    # collections' vector indexes are stored and searched
+    import os
+    app.state.qdrant = QdrantRegistry(
+        engine=_qeng, device=os.environ.get("NORNICDB_QDRANT_DEVICE", "cpu"))
     app.include_router(qdrant_router(app.state.qdrant))
 
     app._tx_commit_body = _tx_commit_body  # reused by the ASGI fast path

@@ -21,15 +21,39 @@ from typing import Any, Dict, List, Optional
 from fastapi import APIRouter, HTTPException
 
 from ..search.embedding_index import EmbeddingIndex
-from ..search.vectorspace import COSINE, GLOBAL, VectorSpace
+from ..search.vectorspace import COSINE, GLOBAL, VectorSpace, normalize_metric
+
+
+def _index_metric(distance: str) -> str:
+    """Metric the collection's index scores with. Cosine, Dot and Euclid are
+    honoured; Manhattan (and anything unknown) is recorded as declared but
+    scored as cosine."""
+    try:
+        return normalize_metric(distance)
+    except ValueError:
+        return COSINE
+
+
+def _index_device(device: str) -> str:
+    """cpu | cuda | auto (cuda when a GPU is present) -> torch device name."""
+    device = (device or "cpu").lower()
+    if device == "auto":
+        import torch
+        return "cuda" if torch.cuda.is_available() else "cpu"
+    if device not in ("cpu", "cuda"):
+        raise ValueError(f"qdrant index device must be cpu, cuda or auto, "
+                         f"got {device!r}")
+    return device
 
 
 class _Collection:
-    def __init__(self, name: str, size: int, distance: str, eng=None):
+    def __init__(self, name: str, size: int, distance: str, eng=None,
+                 device: str = "cpu"):
         self.name = name
         self.size = size
         self.distance = distance
-        self.index = EmbeddingIndex(size, device="cpu")
+        self.index = EmbeddingIndex(size, device=device,
+                                    metric=_index_metric(distance))
         self.payloads: Dict[str, dict] = {}
         self.vectors: Dict[str, list] = {}
         self.created = time.time()
@@ -66,8 +90,12 @@ class _Collection:
 
 
 class QdrantRegistry:
-    def __init__(self, db_name: str = "neo4j", engine=None):
+    def __init__(self, db_name: str = "neo4j", engine=None,
+                 device: str = "cpu"):
         self._lock = threading.Lock()
+        # where the collections' indexes live: "cuda" puts searches on the
+        # fused kNN kernels
+        self.device = _index_device(device)
         self.collections: Dict[str, _Collection] = {}
         self.db_name = db_name
         self.engine = engine
@@ -89,7 +117,7 @@ class QdrantRegistry:
                 continue
             c = _Collection(name, int(props.get("size", 0)),
                             props.get("distance", "Cosine"),
-                            eng=self.engine)
+                            eng=self.engine, device=self.device)
             self.collections[name] = c
             try:
                 GLOBAL.register(VectorSpace(self.db_name, "qdrant", name,
@@ -119,7 +147,8 @@ class QdrantRegistry:
             if name in self.collections:
                 raise KeyError(name)
             self.collections[name] = _Collection(name, size, distance,
-                                                 eng=self.engine)
+                                                 eng=self.engine,
+                                                 device=self.device)
             GLOBAL.register(VectorSpace(self.db_name, "qdrant", name, size,
                                         distance.lower()))
             if self.engine is not None:

@@ -47,6 +47,10 @@ class Config:
     # "" | "int8" | "fp8": 1 B/element GPU corpus (2x capacity; int8
     # keeps recall@10 >= 0.95 worst-case). Also NORNICDB_SEARCH_QUANT.
     search_quant: str = ""
+    # cpu | cuda | auto: device of the Qdrant collections' vector indexes
+    # (cuda searches them with the fused kNN kernels). Also
+    # NORNICDB_QDRANT_DEVICE, which the HTTP server reads.
+    qdrant_device: str = "cpu"
     # observability
     log_queries: bool = False   # reference --log-queries / bolt LogQueries
     # auth
