@@ -81,6 +81,7 @@ void decode_step(at::Tensor layer_ptrs, at::Tensor x, at::Tensor q,
 double sync_bench(long long iters, long long which, long long grid,
                   at::Tensor scratch);
 // knn_fp8.hip
+long long knn_q8_bm_value();
 std::tuple<at::Tensor, at::Tensor> knn_fp8(at::Tensor db, at::Tensor q,
                                            long long row_base, int k_out,
                                            c10::optional<at::Tensor> allow);
@@ -177,6 +178,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n_kv"), py::arg("hd"), py::arg("inter"),
         py::arg("max_len"), py::arg("rms_eps"), py::arg("pos"),
         py::arg("start_tok"), py::arg("n_toks"), py::arg("eos") = -1);
+  // KNN_Q8_BM: rows of one panel of the quantised (int8 / fp8) kNN kernel
+  m.attr("KNN_Q8_BM") = knn_q8_bm_value();
   m.def("knn_i8", &knn_i8,
         "Fused i8 MFMA score + top-k over a symmetric int8 corpus with "
         "per-row scales (score = i32 dot * sa[row] * sq[col])",

@@ -97,6 +97,10 @@ DEV_INLINE float2v hash_gauss2(uint64_t key) {
   return r;
 }
 
+// 1-byte-per-element corpus formats of the quantised kNN and IVF kernels:
+// symmetric int8 with per-row scales, or OCP e4m3fn fp8.
+enum { Q8_FMT_I8 = 0, Q8_FMT_FP8 = 1 };
+
 #define HIP_CHECK_LAST()                                                    \
   do {                                                                      \
     hipError_t _e = hipGetLastError();                                      \

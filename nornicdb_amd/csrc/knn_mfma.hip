@@ -203,6 +203,7 @@
 #include <type_traits>
 #include "common.h"
 #include "allow_mask.h"
+#include "topk.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -369,6 +370,8 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
   // group rg.
   float tv[KCAND];
   int ti[KCAND];
+  // topk_init() written out: with the helper hipcc allocates this kernel's
+  // registers differently (10 more VGPRs unbiased), see NOTES.md
 #pragma unroll
   for (int i = 0; i < KCAND; ++i) { tv[i] = -1e30f; ti[i] = -1; }
   if constexpr (BIASED) {
@@ -601,18 +604,7 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
           bool ok = s > tv[KCAND - 1];
           if constexpr (FILTERED)
             ok = ok && ((aw[m >> 1] >> ((m & 1) * 16 + j)) & 1u);
-          if (ok) {
-            float cs = s;
-            int ci = (int)(grow0 + j);
-#pragma unroll
-            for (int i = 0; i < KCAND; ++i) {
-              bool ins = cs > tv[i];
-              float ts = tv[i]; int tj = ti[i];
-              tv[i] = ins ? cs : tv[i];
-              ti[i] = ins ? ci : ti[i];
-              cs = ins ? ts : cs; ci = ins ? tj : ci;
-            }
-          }
+          if (ok) topk_insert(tv, ti, s, (int)(grow0 + j));
         }
         __builtin_amdgcn_sched_barrier(0);
       });
@@ -636,83 +628,6 @@ __global__ __launch_bounds__(NTHREADS, KNN_WGS) void k_knn_mfma(
   for (int i = 0; i < KCAND; ++i) {
     cand_score[slot * KCAND + i] = tv[i];
     cand_idx[slot * KCAND + i] = ti[i];
-  }
-}
-
-// Merge for int32 local indices -> int64 global (adds row_base).
-template <int K>
-__global__ void k_topk_merge_i32(const float* __restrict__ cand_score,
-                                 const int* __restrict__ cand_idx,
-                                 long long w, int q_stride, int k_out,
-                                 long long row_base,
-                                 float* __restrict__ out_score,
-                                 long long* __restrict__ out_idx) {
-  const int q = blockIdx.x;
-  const long long total = w * K;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  __shared__ unsigned long long s_best[8];
-
-  float tv[K];
-  int ti[K];
-#pragma unroll
-  for (int i = 0; i < K; ++i) { tv[i] = -1e30f; ti[i] = -1; }
-  for (long long j = threadIdx.x; j < total; j += blockDim.x) {
-    long long src = ((j / K) * q_stride + q) * K + (j % K);
-    float s = cand_score[src];
-    if (s > tv[K - 1]) {
-      int ci = cand_idx[src];
-      float cs = s;
-#pragma unroll
-      for (int i = 0; i < K; ++i) {
-        bool ins = cs > tv[i];
-        float ts = tv[i]; int tj = ti[i];
-        tv[i] = ins ? cs : tv[i];
-        ti[i] = ins ? ci : ti[i];
-        cs = ins ? ts : cs; ci = ins ? tj : ci;
-      }
-    }
-  }
-
-  unsigned int mono;
-  int head = 0;
-  for (int r = 0; r < k_out; ++r) {
-    float hv = -1e30f;
-#pragma unroll
-    for (int i = 0; i < K; ++i)
-      if (i == head) hv = tv[i];
-    if (head >= K) hv = -1e30f;
-    {
-      unsigned int u = __float_as_uint(hv);
-      mono = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    unsigned long long packed =
-        ((unsigned long long)mono << 32) | (unsigned int)threadIdx.x;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      unsigned long long o = __shfl_xor(packed, off, WAVE);
-      if (o > packed) packed = o;
-    }
-    if (lane == 0) s_best[wid] = packed;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long b = s_best[0];
-      for (int i = 1; i < (int)(blockDim.x / WAVE); ++i)
-        if (s_best[i] > b) b = s_best[i];
-      s_best[0] = b;
-    }
-    __syncthreads();
-    int winner = (int)(s_best[0] & 0xffffffffu);
-    if (threadIdx.x == winner) {
-      float wv = -1e30f; int wi = -1;
-#pragma unroll
-      for (int i = 0; i < K; ++i)
-        if (i == head) { wv = tv[i]; wi = ti[i]; }
-      out_score[(long long)q * k_out + r] = wv;
-      out_idx[(long long)q * k_out + r] = (wi < 0) ? -1 : row_base + wi;
-      head++;
-    }
-    __syncthreads();
   }
 }
 
@@ -802,11 +717,8 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
 
   at::Tensor out_s = at::empty({BN, k_out}, opts_f);
   at::Tensor out_i = at::empty({BN, k_out}, opts_i64);
-  hipLaunchKernelGGL((k_topk_merge_i32<KCAND>), dim3(BN), dim3(256), 0, stream,
-                     cand_s.data_ptr<float>(), cand_i.data_ptr<int>(), n_lists,
-                     BN, k_out, row_base, out_s.data_ptr<float>(),
-                     reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()));
-  HIP_CHECK_LAST();
+  topk_merge(cand_s, cand_i, n_lists, BN, k_out, row_base, out_s, out_i,
+             stream);
   return {out_s, out_i};
 }
 

@@ -1,6 +1,7 @@
 // Tier-1 vector kernels for NornicDB-AMD: L2 normalize, synthetic corpus
-// generation, fused cosine-score + top-k (GEMV path for small query batches),
-// the cross-block top-k merge, and the IVF probe-list scan.
+// generation, fused cosine-score + top-k (GEMV path for small query batches)
+// and the IVF probe-list scan. Selection itself (register lists, cross-block
+// merge) is topk.h.
 //
 // Re-designs (not ports of) the reference's CUDA kernels
 // (reference: pkg/gpu/cuda/cuda_kernels.cu:185-460 — 1-thread-per-vector
@@ -12,6 +13,7 @@
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
 #include "allow_mask.h"
+#include "topk.h"
 
 // ---------------------------------------------------------------------------
 // L2 normalize rows, in-place. bf16 [N][D], D % 8 == 0.
@@ -177,8 +179,7 @@ __global__ void k_knn_gemv_bf16(const unsigned short* __restrict__ db,
   // private top-K (valid in lane gl == q for q < q_count)
   float tv[K];
   long long ti[K];
-#pragma unroll
-  for (int i = 0; i < K; ++i) { tv[i] = -1e30f; ti[i] = -1; }
+  topk_init(tv, ti);
 
   for (long long row = group_global; row < n; row += total_groups) {
     if constexpr (FILTERED) {
@@ -225,17 +226,7 @@ __global__ void k_knn_gemv_bf16(const unsigned short* __restrict__ db,
       for (int q = 1; q < QMAX; ++q)
         if (gl == q) s = acc[q];
       if constexpr (BIASED) s += rb;
-      if (s > tv[K - 1]) {
-        float cs = s; long long ci = row_base + row;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-          bool ins = cs > tv[i];
-          float ts = tv[i]; long long tj = ti[i];
-          tv[i] = ins ? cs : tv[i];
-          ti[i] = ins ? ci : ti[i];
-          cs = ins ? ts : cs; ci = ins ? tj : ci;
-        }
-      }
+      if (s > tv[K - 1]) topk_insert(tv, ti, s, row_base + row);
     }
   }
 
@@ -246,99 +237,6 @@ __global__ void k_knn_gemv_bf16(const unsigned short* __restrict__ db,
       cand_score[base + i] = tv[i];
       cand_idx[base + i] = ti[i];
     }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Merge per-block candidate lists into final top-k.
-// cand_*: [W][Q][K]; one block per query; K rounds of packed argmax-reduce.
-// Packs (monotonic_score_bits << 32 | slot) into uint64 for the reduce.
-// ---------------------------------------------------------------------------
-DEV_INLINE unsigned int f32_mono(float f) {
-  unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-DEV_INLINE float mono_f32(unsigned int m) {
-  unsigned int u = (m & 0x80000000u) ? (m & 0x7fffffffu) : ~m;
-  return __uint_as_float(u);
-}
-
-// Always launched with 256 threads; the bound lets K=64 keep its lists in
-// registers (192 of them) instead of spilling at the default 128-VGPR cap.
-template <int K>
-__global__ void __launch_bounds__(256)
-k_topk_merge(const float* __restrict__ cand_score,
-                             const long long* __restrict__ cand_idx,
-                             long long w, int q_count, int k_out,
-                             float* __restrict__ out_score,
-                             long long* __restrict__ out_idx) {
-  const int q = blockIdx.x;
-  const long long total = w * K;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  __shared__ unsigned long long s_best[8];
-
-  // each thread scans strided candidates into a private top-K
-  float tv[K];
-  long long ti[K];
-#pragma unroll
-  for (int i = 0; i < K; ++i) { tv[i] = -1e30f; ti[i] = -1; }
-  for (long long j = threadIdx.x; j < total; j += blockDim.x) {
-    long long src = ((j / K) * q_count + q) * K + (j % K);
-    float s = cand_score[src];
-    if (s > tv[K - 1]) {
-      long long ci = cand_idx[src];
-      float cs = s;
-#pragma unroll
-      for (int i = 0; i < K; ++i) {
-        bool ins = cs > tv[i];
-        float ts = tv[i]; long long tj = ti[i];
-        tv[i] = ins ? cs : tv[i];
-        ti[i] = ins ? ci : ti[i];
-        cs = ins ? ts : cs; ci = ins ? tj : ci;
-      }
-    }
-  }
-
-  // k_out rounds: global argmax over every thread's current head element.
-  int head = 0;
-  for (int r = 0; r < k_out; ++r) {
-    float hv = -1e30f;
-    // select current head value via static unroll (keeps tv in registers)
-#pragma unroll
-    for (int i = 0; i < K; ++i)
-      if (i == head) hv = tv[i];
-    if (head >= K) hv = -1e30f;
-    unsigned long long packed =
-        ((unsigned long long)f32_mono(hv) << 32) | (unsigned int)threadIdx.x;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      unsigned long long o = __shfl_xor(packed, off, WAVE);
-      if (o > packed) packed = o;
-    }
-    if (lane == 0) s_best[wid] = packed;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long b = s_best[0];
-      for (int i = 1; i < blockDim.x / WAVE; ++i)
-        if (s_best[i] > b) b = s_best[i];
-      s_best[0] = b;
-    }
-    __syncthreads();
-    unsigned long long b = s_best[0];
-    int winner = (int)(b & 0xffffffffu);
-    if (threadIdx.x == winner) {
-      float wv = tv[0];
-      long long wi = ti[0];
-#pragma unroll
-      for (int i = 0; i < K; ++i)
-        if (i == head) { wv = tv[i]; wi = ti[i]; }
-      out_score[(long long)q * k_out + r] = wv;
-      out_idx[(long long)q * k_out + r] = wi;
-      head++;
-    }
-    __syncthreads();
-    // re-broadcast head increment handled per-thread (winner only)
   }
 }
 
@@ -359,14 +257,115 @@ k_topk_merge(const float* __restrict__ cand_score,
 // K-lists. They go to LDS and each of the 16*K entries finds its rank in
 // the union by a binary search in every list (ties broken by position, so
 // ranks are a permutation); ranks < K are written out. That leaves ONE
-// candidate list per block for k_topk_merge, in its [W][Q][K] layout with
+// candidate list per block for topk_merge(), in its [W][Q][K] layout with
 // W = p_eff * split.
 //
 // A probe outside [0, n_lists), or equal to an earlier probe of the same
 // query, scans nothing. List entries are accepted only when they name a
 // row below tail_start, so no row is scored twice or read out of bounds.
 // FILTERED tests the allow bit before the row is loaded (allow_mask.h).
+//
+// ivf_block(), ivf_list_range() and ivf_rank_merge() are the parts every
+// scan kernel shares.
 // ---------------------------------------------------------------------------
+
+// A block's split, probe slot and query; block-uniform.
+struct IvfBlock {
+  int sp, p, q;
+};
+
+DEV_INLINE IvfBlock ivf_block(int p_eff, int split) {
+  IvfBlock b;
+  b.sp = blockIdx.x % split;
+  b.p = (blockIdx.x / split) % p_eff;
+  b.q = blockIdx.x / (split * p_eff);
+  return b;
+}
+
+// The entries [begin, end) of a block's list; block-uniform. An empty range
+// means there is nothing to scan. Kernels call this behind their query
+// staging loop: the dependent scalar loads (probe, then list offsets) then
+// run behind the staging loads instead of in front of them, which measured
+// ~1 us per call on the quantised scans.
+struct IvfRange {
+  bool tail;
+  long long begin, end;
+  unsigned int row_limit;  // entries must name a row below this
+};
+
+DEV_INLINE IvfRange ivf_list_range(const IvfBlock& b,
+                                   const int* __restrict__ probes,
+                                   const int* __restrict__ list_off,
+                                   int n_lists, long long n_entries,
+                                   int n_probe, int tail_start, int n) {
+  IvfRange r;
+  r.tail = (b.p == n_probe);
+  r.begin = 0;
+  r.end = 0;
+  if (r.tail) {
+    r.begin = tail_start;
+    r.end = n;
+  } else {
+    const int* pq = probes + (long long)b.q * n_probe;
+    const int c = pq[b.p];
+    if (c >= 0 && c < n_lists) {
+      bool dup = false;
+      for (int j = 0; j < b.p; ++j) dup |= (pq[j] == c);
+      if (!dup) {
+        r.begin = max(list_off[c], 0);
+        r.end = min((long long)list_off[c + 1], n_entries);
+      }
+    }
+  }
+  r.row_limit = r.tail ? (unsigned int)n : (unsigned int)tail_start;
+  return r;
+}
+
+// The block's 16 sorted K-lists (one per lane group g16, identical in the
+// group's 16 lanes) go to LDS; every entry finds its rank in their union and
+// ranks < K are written to the block's candidate list at out_base. Contains
+// a __syncthreads(): every thread of the block calls it.
+template <int K>
+DEV_INLINE void ivf_rank_merge(const float (&tv)[K], const int (&ti)[K],
+                               int g16, int gl, float* s_ls, int* s_li,
+                               long long out_base, long long row_base,
+                               float* __restrict__ cand_score,
+                               long long* __restrict__ cand_idx) {
+  if (gl == 0) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      s_ls[g16 * K + i] = tv[i];
+      s_li[g16 * K + i] = ti[i];
+    }
+  }
+  __syncthreads();
+
+  for (int x = threadIdx.x; x < 16 * K; x += blockDim.x) {
+    const float xs = s_ls[x];
+    int rank = 0;
+#pragma unroll 4
+    for (int l = 0; l < 16; ++l) {
+      const float* ls = s_ls + l * K;
+      const int pos0 = l * K;
+      int lo = 0;
+#pragma unroll
+      for (int step = K / 2; step >= 1; step >>= 1) {
+        const int j = lo + step - 1;
+        const float a = ls[j];
+        lo += (a > xs || (a == xs && pos0 + j < x)) ? step : 0;
+      }
+      const float a = ls[lo];
+      lo += (a > xs || (a == xs && pos0 + lo < x)) ? 1 : 0;
+      rank += lo;
+    }
+    if (rank < K) {
+      const int r = s_li[x];
+      cand_score[out_base + rank] = xs;
+      cand_idx[out_base + rank] = r < 0 ? -1LL : row_base + (long long)r;
+    }
+  }
+}
+
 template <int K, bool FILTERED>
 __global__ void __launch_bounds__(256)
 k_ivf_scan_bf16(const unsigned short* __restrict__ db,
@@ -391,40 +390,23 @@ k_ivf_scan_bf16(const unsigned short* __restrict__ db,
   const int wid = threadIdx.x / WAVE;
   const int g16 = wid * 4 + grp;    // lane-group within the block, 0..15
 
-  const int sp = blockIdx.x % split;
-  const int p = (blockIdx.x / split) % p_eff;
-  const int q = blockIdx.x / (split * p_eff);
+  const IvfBlock blk = ivf_block(p_eff, split);
+  const int sp = blk.sp, p = blk.p, q = blk.q;
 
   for (int i = threadIdx.x * 8; i < d; i += blockDim.x * 8) {
     *reinterpret_cast<short8v*>(s_q + i) =
         *reinterpret_cast<const short8v*>(qs + (long long)q * d + i);
   }
-
-  // entries [begin, end) of this block's list; block-uniform
-  const bool tail = (p == n_probe);
-  long long begin = 0, end = 0;
-  if (tail) {
-    begin = tail_start;
-    end = n;
-  } else {
-    const int* pq = probes + (long long)q * n_probe;
-    const int c = pq[p];
-    if (c >= 0 && c < n_lists) {
-      bool dup = false;
-      for (int j = 0; j < p; ++j) dup |= (pq[j] == c);
-      if (!dup) {
-        begin = max(list_off[c], 0);
-        end = min((long long)list_off[c + 1], n_entries);
-      }
-    }
-  }
-  const unsigned int row_limit = tail ? (unsigned int)n : (unsigned int)tail_start;
+  const IvfRange rng = ivf_list_range(blk, probes, list_off, n_lists, n_entries,
+                                      n_probe, tail_start, n);
+  const bool tail = rng.tail;
+  const long long begin = rng.begin, end = rng.end;
+  const unsigned int row_limit = rng.row_limit;
   __syncthreads();
 
   float tv[K];
   int ti[K];
-#pragma unroll
-  for (int i = 0; i < K; ++i) { tv[i] = -1e30f; ti[i] = -1; }
+  topk_init(tv, ti);
 
   const int nj = d / 128;
   const long long stride = (long long)split * 16;
@@ -458,76 +440,38 @@ k_ivf_scan_bf16(const unsigned short* __restrict__ db,
       for (int off = 1; off < 16; off <<= 1)
         acc += __shfl_xor(acc, off, WAVE);
       // same score in all 16 lanes of the group: uniform insert
-      if (acc > tv[K - 1]) {
-        float cs = acc; int ci = row;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-          bool ins = cs > tv[i];
-          float ts = tv[i]; int tj = ti[i];
-          tv[i] = ins ? cs : tv[i];
-          ti[i] = ins ? ci : ti[i];
-          cs = ins ? ts : cs; ci = ins ? tj : ci;
-        }
-      }
+      if (acc > tv[K - 1]) topk_insert(tv, ti, acc, row);
     }
     e = e_next;
     row = row_next;
   }
 
-  if (gl == 0) {
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-      s_ls[g16 * K + i] = tv[i];
-      s_li[g16 * K + i] = ti[i];
-    }
-  }
-  __syncthreads();
-
   // rank of every entry in the union of the 16 sorted lists
   const long long out_base =
       (((long long)p * split + sp) * q_count + q) * K;
-  for (int x = threadIdx.x; x < 16 * K; x += blockDim.x) {
-    const float xs = s_ls[x];
-    int rank = 0;
-#pragma unroll 4
-    for (int l = 0; l < 16; ++l) {
-      const float* ls = s_ls + l * K;
-      const int pos0 = l * K;
-      int lo = 0;
-#pragma unroll
-      for (int step = K / 2; step >= 1; step >>= 1) {
-        const int j = lo + step - 1;
-        const float a = ls[j];
-        lo += (a > xs || (a == xs && pos0 + j < x)) ? step : 0;
-      }
-      const float a = ls[lo];
-      lo += (a > xs || (a == xs && pos0 + lo < x)) ? 1 : 0;
-      rank += lo;
-    }
-    if (rank < K) {
-      const int r = s_li[x];
-      cand_score[out_base + rank] = xs;
-      cand_idx[out_base + rank] = r < 0 ? -1LL : row_base + (long long)r;
-    }
-  }
+  ivf_rank_merge(tv, ti, g16, gl, s_ls, s_li, out_base, row_base, cand_score,
+                 cand_idx);
 }
 
 // ---------------------------------------------------------------------------
 // The same scan over a 1-byte-per-element corpus: symmetric int8 with
 // per-row scales, or OCP e4m3 fp8. Block contract, list walk, insert and
-// epilogue are those of k_ivf_scan_bf16 (its text is repeated, not shared,
-// so that kernel's register allocation stays as measured); only the row
-// score differs. A row is d contiguous bytes: per 128 elements each of a
-// group's 16 lanes loads 8 of them, against 8 query bytes from LDS.
+// epilogue are those of k_ivf_scan_bf16; only the row score differs. The
+// block decode (ivf_block, ivf_list_range), the insert (topk.h) and the epilogue
+// (ivf_rank_merge) are shared as force-inlined helpers: compiled with them,
+// every scan kernel keeps the registers, LDS and zero scratch it had with
+// its own copy of the text (table in profiles/README.md, "Top-k core
+// refactor"). The list walk is still written out in both kernels. A row is
+// d contiguous bytes: per 128 elements each of a group's 16 lanes loads 8
+// of them, against 8 query bytes from LDS.
 //
 // int8: the query arrives quantised (int8 [Q][d] and its scale sq[q]);
 //   v_dot4 accumulates into an int32 that the butterfly reduces exactly,
-//   score = float(dot) * sa[row] * sq[q] as in k_knn_i8. sa is indexed by
+//   score = float(dot) * sa[row] * sq[q] as in k_knn_q8. sa is indexed by
 //   slot number and loaded ahead of the row's data.
 // fp8: row and query bytes are converted in pairs (v_cvt_pk_f32_fp8, exact)
 //   and accumulated in fp32.
 // ---------------------------------------------------------------------------
-enum { IVF_FMT_I8 = 0, IVF_FMT_FP8 = 1 };
 typedef unsigned int uint2v __attribute__((ext_vector_type(2)));   // 8B
 
 template <int K, bool FILTERED, int FMT>
@@ -556,42 +500,25 @@ k_ivf_scan_q8(const unsigned char* __restrict__ db,
   const int wid = threadIdx.x / WAVE;
   const int g16 = wid * 4 + grp;    // lane-group within the block, 0..15
 
-  const int sp = blockIdx.x % split;
-  const int p = (blockIdx.x / split) % p_eff;
-  const int q = blockIdx.x / (split * p_eff);
+  const IvfBlock blk = ivf_block(p_eff, split);
+  const int sp = blk.sp, p = blk.p, q = blk.q;
 
   for (int i = threadIdx.x * 8; i < d; i += blockDim.x * 8) {
     *reinterpret_cast<uint2v*>(s_q + i) =
         *reinterpret_cast<const uint2v*>(qs + (long long)q * d + i);
   }
   float q_scale = 1.0f;
-  if constexpr (FMT == IVF_FMT_I8) q_scale = sq[q];
-
-  // entries [begin, end) of this block's list; block-uniform
-  const bool tail = (p == n_probe);
-  long long begin = 0, end = 0;
-  if (tail) {
-    begin = tail_start;
-    end = n;
-  } else {
-    const int* pq = probes + (long long)q * n_probe;
-    const int c = pq[p];
-    if (c >= 0 && c < n_lists) {
-      bool dup = false;
-      for (int j = 0; j < p; ++j) dup |= (pq[j] == c);
-      if (!dup) {
-        begin = max(list_off[c], 0);
-        end = min((long long)list_off[c + 1], n_entries);
-      }
-    }
-  }
-  const unsigned int row_limit = tail ? (unsigned int)n : (unsigned int)tail_start;
+  if constexpr (FMT == Q8_FMT_I8) q_scale = sq[q];
+  const IvfRange rng = ivf_list_range(blk, probes, list_off, n_lists, n_entries,
+                                      n_probe, tail_start, n);
+  const bool tail = rng.tail;
+  const long long begin = rng.begin, end = rng.end;
+  const unsigned int row_limit = rng.row_limit;
   __syncthreads();
 
   float tv[K];
   int ti[K];
-#pragma unroll
-  for (int i = 0; i < K; ++i) { tv[i] = -1e30f; ti[i] = -1; }
+  topk_init(tv, ti);
 
   const int nj = d / 128;
   const long long stride = (long long)split * 16;
@@ -612,7 +539,7 @@ k_ivf_scan_q8(const unsigned char* __restrict__ db,
       const unsigned char* rp = db + (long long)row * d + gl * 8;
       const unsigned char* qp = s_q + gl * 8;
       float score;
-      if constexpr (FMT == IVF_FMT_I8) {
+      if constexpr (FMT == Q8_FMT_I8) {
         // its own cache line per row: in flight with the row's data
         const float row_scale = sa[row];
         int acc = 0;
@@ -652,58 +579,17 @@ k_ivf_scan_q8(const unsigned char* __restrict__ db,
         score = acc;
       }
       // same score in all 16 lanes of the group: uniform insert
-      if (score > tv[K - 1]) {
-        float cs = score; int ci = row;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-          bool ins = cs > tv[i];
-          float ts = tv[i]; int tj = ti[i];
-          tv[i] = ins ? cs : tv[i];
-          ti[i] = ins ? ci : ti[i];
-          cs = ins ? ts : cs; ci = ins ? tj : ci;
-        }
-      }
+      if (score > tv[K - 1]) topk_insert(tv, ti, score, row);
     }
     e = e_next;
     row = row_next;
   }
 
-  if (gl == 0) {
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-      s_ls[g16 * K + i] = tv[i];
-      s_li[g16 * K + i] = ti[i];
-    }
-  }
-  __syncthreads();
-
   // rank of every entry in the union of the 16 sorted lists
   const long long out_base =
       (((long long)p * split + sp) * q_count + q) * K;
-  for (int x = threadIdx.x; x < 16 * K; x += blockDim.x) {
-    const float xs = s_ls[x];
-    int rank = 0;
-#pragma unroll 4
-    for (int l = 0; l < 16; ++l) {
-      const float* ls = s_ls + l * K;
-      const int pos0 = l * K;
-      int lo = 0;
-#pragma unroll
-      for (int step = K / 2; step >= 1; step >>= 1) {
-        const int j = lo + step - 1;
-        const float a = ls[j];
-        lo += (a > xs || (a == xs && pos0 + j < x)) ? step : 0;
-      }
-      const float a = ls[lo];
-      lo += (a > xs || (a == xs && pos0 + lo < x)) ? 1 : 0;
-      rank += lo;
-    }
-    if (rank < K) {
-      const int r = s_li[x];
-      cand_score[out_base + rank] = xs;
-      cand_idx[out_base + rank] = r < 0 ? -1LL : row_base + (long long)r;
-    }
-  }
+  ivf_rank_merge(tv, ti, g16, gl, s_ls, s_li, out_base, row_base, cand_score,
+                 cand_idx);
 }
 
 // ===========================================================================
@@ -803,11 +689,8 @@ std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
 
   at::Tensor out_s = at::empty({qc, k_out}, opts_f);
   at::Tensor out_i = at::empty({qc, k_out}, opts_i);
-  hipLaunchKernelGGL((k_topk_merge<KNN_K>), dim3(qc), dim3(256), 0,
-                     cur_stream(), cand_s.data_ptr<float>(),
-                     reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()), waves, qc, k_out,
-                     out_s.data_ptr<float>(), reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()));
-  HIP_CHECK_LAST();
+  // candidates hold global ids already
+  topk_merge(cand_s, cand_i, waves, qc, k_out, 0, out_s, out_i, cur_stream());
   return {out_s, out_i};
 }
 
@@ -912,12 +795,9 @@ static std::tuple<at::Tensor, at::Tensor> ivf_scan_merge(
   scan(dim3((unsigned)(w * pl.qc)), lds, cand_s.data_ptr<float>(),
        reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()));
   HIP_CHECK_LAST();
-  hipLaunchKernelGGL((k_topk_merge<K>), dim3(pl.qc), dim3(256), 0,
-                     cur_stream(), cand_s.data_ptr<float>(),
-                     reinterpret_cast<long long*>(cand_i.data_ptr<int64_t>()),
-                     w, pl.qc, pl.k_out, out_s.data_ptr<float>(),
-                     reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()));
-  HIP_CHECK_LAST();
+  // the scan added row_base to its ids
+  topk_merge(cand_s, cand_i, w, pl.qc, pl.k_out, 0, out_s, out_i,
+             cur_stream());
   return {out_s, out_i};
 }
 
@@ -1007,9 +887,9 @@ std::tuple<at::Tensor, at::Tensor> ivf_scan_i8(
   const float* sap = sa.data_ptr<float>();
   const float* sqp = sq.data_ptr<float>();
   if (k_out <= 16)
-    return ivf_scan_q8_run<16, IVF_FMT_I8>(who, pl, db, q, sap, sqp, probes,
+    return ivf_scan_q8_run<16, Q8_FMT_I8>(who, pl, db, q, sap, sqp, probes,
                                            list_off, list_rows);
-  return ivf_scan_q8_run<64, IVF_FMT_I8>(who, pl, db, q, sap, sqp, probes,
+  return ivf_scan_q8_run<64, Q8_FMT_I8>(who, pl, db, q, sap, sqp, probes,
                                          list_off, list_rows);
 }
 
@@ -1024,8 +904,8 @@ std::tuple<at::Tensor, at::Tensor> ivf_scan_fp8(
                                    allow);
   if (pl.p_eff == 0) return ivf_nothing_to_scan(pl, db);
   if (k_out <= 16)
-    return ivf_scan_q8_run<16, IVF_FMT_FP8>(who, pl, db, q, nullptr, nullptr,
+    return ivf_scan_q8_run<16, Q8_FMT_FP8>(who, pl, db, q, nullptr, nullptr,
                                             probes, list_off, list_rows);
-  return ivf_scan_q8_run<64, IVF_FMT_FP8>(who, pl, db, q, nullptr, nullptr,
+  return ivf_scan_q8_run<64, Q8_FMT_FP8>(who, pl, db, q, nullptr, nullptr,
                                           probes, list_off, list_rows);
 }

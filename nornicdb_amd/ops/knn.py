@@ -40,7 +40,15 @@ def _knn_bm() -> int:
     return int(getattr(nat, "KNN_BM", 96)) if nat is not None else 96
 
 
+def _knn_q8_bm() -> int:
+    """Panel row count of the quantised (int8 / fp8) kernel, 96: the same
+    role as _knn_bm for csrc/knn_fp8.hip."""
+    nat = native_or_none()
+    return int(getattr(nat, "KNN_Q8_BM", 96)) if nat is not None else 96
+
+
 _NEG_INF = float("-inf")
+_QMAX = 256  # query columns of one MFMA kernel launch
 
 
 def pack_allow_mask(allow: torch.Tensor) -> torch.Tensor:
@@ -108,6 +116,49 @@ def _pad_unfilled(s, i):
     return s.masked_fill(i < 0, _NEG_INF), i
 
 
+def _merge_topk(best, new, k):
+    """Running best (scores, ids), (None, None) at the start, merged with
+    another row range's top-k."""
+    if best[0] is None:
+        return new
+    cs = torch.cat([best[0], new[0]], dim=-1)
+    ci = torch.cat([best[1], new[1]], dim=-1)
+    s, sel = torch.topk(cs, min(k, cs.shape[-1]), dim=-1)
+    return s, torch.gather(ci, -1, sel)
+
+
+def _chunked_topk(score_rows, n, k, row_base, allow, chunk_rows=4 << 20,
+                  start=0, best=(None, None)):
+    """top-k over rows [start, n) in torch, chunk_rows at a time, on top of
+    `best`. score_rows(a, b) returns the fp32 scores [Q, b - a] of rows
+    a..b."""
+    for a in range(start, n, chunk_rows):
+        b = min(a + chunk_rows, n)
+        ok = None if allow is None else _mask_rows(allow, a, b)
+        top = _masked_topk(score_rows(a, b), ok, min(k, b - a), row_base + a)
+        best = _merge_topk(best, top, k)
+    return best
+
+
+def _by_query_batches(search, q):
+    """search(q) for up to _QMAX queries; larger batches (multi-GPU
+    all-gather) go through it _QMAX queries at a time."""
+    if q.shape[0] <= _QMAX:
+        return search(q)
+    parts = [search(q[s:s + _QMAX]) for s in range(0, q.shape[0], _QMAX)]
+    return (torch.cat([p[0] for p in parts], 0),
+            torch.cat([p[1] for p in parts], 0))
+
+
+def _pad_queries(x):
+    """Zero rows up to the _QMAX the MFMA kernels take."""
+    if x.shape[0] == _QMAX:
+        return x
+    pad = torch.zeros(_QMAX - x.shape[0], *x.shape[1:], dtype=x.dtype,
+                      device=x.device)
+    return torch.cat([x, pad])
+
+
 def knn_search_exact(
     db: torch.Tensor, q: torch.Tensor, k: int, row_base: int = 0,
     allow: Optional[torch.Tensor] = None,
@@ -131,30 +182,18 @@ def _knn_gemm_chunked(
     With a row bias the product is taken in fp32, in chunks small enough for
     an fp32 copy: a bf16 GEMM rounds its output to 8 bits, and q.x + bias
     cancels (a Euclidean bias is -|x|^2/2 against q.x of the same size)."""
-    n = db.shape[0]
     qf = q.to(db.dtype)
     if row_bias is not None:
         chunk_rows = min(chunk_rows, 1 << 18)
         qf = q.float()
-    best_s = None
-    best_i = None
-    for start in range(0, n, chunk_rows):
-        stop = min(start + chunk_rows, n)
+
+    def score_rows(start, stop):
         if row_bias is None:
-            scores = (qf @ db[start:stop].T).float()  # [Q, chunk]
-        else:
-            scores = qf @ db[start:stop].float().T + row_bias[start:stop]
-        kk = min(k, stop - start)
-        ok = None if allow is None else _mask_rows(allow, start, stop)
-        s, i = _masked_topk(scores, ok, kk, row_base + start)
-        if best_s is None:
-            best_s, best_i = s, i
-        else:
-            cs = torch.cat([best_s, s], dim=-1)
-            ci = torch.cat([best_i, i], dim=-1)
-            best_s, sel = torch.topk(cs, min(k, cs.shape[-1]), dim=-1)
-            best_i = torch.gather(ci, -1, sel)
-    return best_s, best_i
+            return (qf @ db[start:stop].T).float()  # [Q, chunk]
+        return qf @ db[start:stop].float().T + row_bias[start:stop]
+
+    return _chunked_topk(score_rows, db.shape[0], k, row_base, allow,
+                         chunk_rows)
 
 
 def _check_row_bias(row_bias: torch.Tensor, db: torch.Tensor) -> torch.Tensor:
@@ -214,15 +253,10 @@ def _knn_dispatch(db, q, k, row_base, allow, row_bias=None):
         nat = native_or_none()
         if nat is None:
             require_native()
-        if k <= 10 and db.shape[1] % 128 == 0 and db.shape[0] >= 96:
-            if q.shape[0] <= 256:
-                return _knn_fp8(nat, db, q, k, row_base, allow)
-            ss, ii = [], []
-            for s in range(0, q.shape[0], 256):
-                cs, ci = _knn_fp8(nat, db, q[s:s + 256], k, row_base, allow)
-                ss.append(cs)
-                ii.append(ci)
-            return torch.cat(ss, 0), torch.cat(ii, 0)
+        if (k <= 10 and db.shape[1] % 128 == 0
+                and db.shape[0] >= _knn_q8_bm()):
+            return _by_query_batches(
+                lambda qq: _knn_fp8(nat, db, qq, k, row_base, allow), q)
         return _knn_fp8_chunked(db, q, k, row_base, allow=allow)
 
     nat = native_or_none()
@@ -245,17 +279,8 @@ def _knn_dispatch(db, q, k, row_base, allow, row_bias=None):
         and db.shape[1] % 64 == 0
         and db.shape[0] >= _knn_bm()
     ):
-        if q.shape[0] <= 256:
-            return _knn_mfma(nat, db, q, k, row_base, allow, row_bias)
-        # large query batches (multi-GPU all-gather): chunk through the
-        # fused kernel 256 queries at a time
-        ss, ii = [], []
-        for s in range(0, q.shape[0], 256):
-            cs, ci = _knn_mfma(nat, db, q[s:s + 256], k, row_base, allow,
-                               row_bias)
-            ss.append(cs)
-            ii.append(ci)
-        return torch.cat(ss, 0), torch.cat(ii, 0)
+        return _by_query_batches(
+            lambda qq: _knn_mfma(nat, db, qq, k, row_base, allow, row_bias), q)
     if (
         q.shape[0] <= 16
         and k <= 16
@@ -315,152 +340,90 @@ def knn_search_int8(
 
 
 def _knn_int8_dispatch(db, sa, q, k, row_base, allow):
-    qi, sq = quantize_int8(q)
     if not db.is_cuda:
+        qi, sq = quantize_int8(q)
         scores = (qi.float() * sq[:, None]) @ (db.float() * sa[:, None]).T
         ok = None if allow is None else _mask_rows(allow, 0, db.shape[0])
         return _masked_topk(scores, ok, k, row_base)
     nat = native_or_none()
     if nat is None:
         require_native()
-    if k <= 10 and db.shape[1] % 128 == 0 and db.shape[0] >= 96:
-        if q.shape[0] > 256:
-            ss, ii = [], []
-            for s0 in range(0, q.shape[0], 256):
-                cs, ci = _knn_int8_dispatch(db, sa, q[s0:s0 + 256], k,
-                                            row_base, allow)
-                ss.append(cs)
-                ii.append(ci)
-            return torch.cat(ss, 0), torch.cat(ii, 0)
-        qn = q.shape[0]
-        if qn < 256:
-            qi = torch.cat([qi, torch.zeros(256 - qn, q.shape[1],
-                                            dtype=torch.int8,
-                                            device=q.device)])
-            sq = torch.cat([sq, torch.zeros(256 - qn, device=q.device)])
-        n = db.shape[0]
-        n_main = (n // 96) * 96
-        s, i = nat.knn_i8(db.narrow(0, 0, n_main).contiguous(),
-                          sa.narrow(0, 0, n_main).contiguous().float(),
-                          qi.contiguous(), sq.contiguous().float(),
-                          row_base, k, allow)
-        s, i = s[:qn], i[:qn]
-        if n_main < n:
-            tail = db.narrow(0, n_main, n - n_main)
-            tsa = sa.narrow(0, n_main, n - n_main)
-            ts = (qi[:qn].float() * sq[:qn, None]) @ \
-                 (tail.float() * tsa[:, None]).T
-            kk = min(k, n - n_main)
-            ok = None if allow is None else _mask_rows(allow, n_main, n)
-            bs, bi = _masked_topk(ts, ok, kk, row_base + n_main)
-            cs = torch.cat([s, bs], -1)
-            ci = torch.cat([i, bi], -1)
-            s, sel = torch.topk(cs, k, dim=-1)
-            i = torch.gather(ci, -1, sel)
-        return s, i
+    if k <= 10 and db.shape[1] % 128 == 0 and db.shape[0] >= _knn_q8_bm():
+        return _by_query_batches(
+            lambda qq: _knn_int8(nat, db, sa, qq, k, row_base, allow), q)
     # k > 10 / odd dims: chunked dequantized scoring
-    n = db.shape[0]
-    best_s = best_i = None
+    qi, sq = quantize_int8(q)
     qf = (qi.float() * sq[:, None]).to(torch.bfloat16)
-    for start in range(0, n, 4 << 20):
-        stop = min(start + (4 << 20), n)
+
+    def score_rows(start, stop):
         chunk = (db[start:stop].float() * sa[start:stop, None]).to(torch.bfloat16)
-        scores = (qf @ chunk.T).float()
-        kk = min(k, stop - start)
-        ok = None if allow is None else _mask_rows(allow, start, stop)
-        s, i = _masked_topk(scores, ok, kk, row_base + start)
-        if best_s is None:
-            best_s, best_i = s, i
-        else:
-            cs = torch.cat([best_s, s], dim=-1)
-            ci = torch.cat([best_i, i], dim=-1)
-            best_s, sel = torch.topk(cs, min(k, cs.shape[-1]), dim=-1)
-            best_i = torch.gather(ci, -1, sel)
-    return best_s, best_i
+        return (qf @ chunk.T).float()
+
+    return _chunked_topk(score_rows, db.shape[0], k, row_base, allow)
+
+
+def _knn_int8(nat, db, sa, q, k, row_base, allow=None):
+    """Fused i8 MFMA score+topk over full panels + torch-scored tail, both
+    on the int8-quantised q."""
+    qn = q.shape[0]
+    qi, sq = quantize_int8(q)
+    n = db.shape[0]
+    n_main = (n // _knn_q8_bm()) * _knn_q8_bm()
+    s, i = nat.knn_i8(db.narrow(0, 0, n_main).contiguous(),
+                      sa.narrow(0, 0, n_main).contiguous().float(),
+                      _pad_queries(qi).contiguous(),
+                      _pad_queries(sq).contiguous().float(),
+                      row_base, k, allow)
+    qd = qi.float() * sq[:, None]
+    return _chunked_topk(
+        lambda a, b: qd @ (db[a:b].float() * sa[a:b, None]).T,
+        n, k, row_base, allow, start=n_main, best=(s[:qn], i[:qn]))
 
 
 def _knn_fp8(nat, db, q, k, row_base, allow=None):
-    """Fused fp8 MFMA score+topk over full 96-row panels + torch tail.
+    """Fused fp8 MFMA score+topk over full panels + torch tail.
 
     q is quantized to e4m3fn so main-panel and tail scores agree
     (both score the same representable values)."""
     qn = q.shape[0]
     q8 = q.to(torch.float8_e4m3fn)
-    if qn < 256:
-        q8 = torch.cat([q8, torch.zeros(256 - qn, q.shape[1],
-                                        dtype=torch.float8_e4m3fn,
-                                        device=q.device)])
-    qu = q8.contiguous().view(torch.uint8)
+    qu = _pad_queries(q8).contiguous().view(torch.uint8)
     n = db.shape[0]
-    n_main = (n // 96) * 96
+    n_main = (n // _knn_q8_bm()) * _knn_q8_bm()
     s, i = nat.knn_fp8(db.narrow(0, 0, n_main).view(torch.uint8), qu,
                        row_base, k, allow)
-    s, i = s[:qn], i[:qn]
-    if n_main < n:
-        tail = db.narrow(0, n_main, n - n_main).to(torch.bfloat16)
-        ts = (q8[:qn].to(torch.bfloat16) @ tail.T).float()
-        kk = min(k, n - n_main)
-        ok = None if allow is None else _mask_rows(allow, n_main, n)
-        bs, bi = _masked_topk(ts, ok, kk, row_base + n_main)
-        cs = torch.cat([s, bs], -1)
-        ci = torch.cat([i, bi], -1)
-        s, sel = torch.topk(cs, k, dim=-1)
-        i = torch.gather(ci, -1, sel)
-    return s, i
+    qb = q8.to(torch.bfloat16)
+    return _chunked_topk(
+        lambda a, b: (qb @ db[a:b].to(torch.bfloat16).T).float(),
+        n, k, row_base, allow, start=n_main, best=(s[:qn], i[:qn]))
 
 
 def _knn_fp8_chunked(db, q, k, row_base, chunk_rows: int = 4 << 20,
                      allow=None):
     """Dequantize-per-chunk fallback (k > 10 or odd dims)."""
-    n = db.shape[0]
     qf = q.to(torch.bfloat16)
-    best_s = best_i = None
-    for start in range(0, n, chunk_rows):
-        stop = min(start + chunk_rows, n)
-        scores = (qf @ db[start:stop].to(torch.bfloat16).T).float()
-        kk = min(k, stop - start)
-        ok = None if allow is None else _mask_rows(allow, start, stop)
-        s, i = _masked_topk(scores, ok, kk, row_base + start)
-        if best_s is None:
-            best_s, best_i = s, i
-        else:
-            cs = torch.cat([best_s, s], dim=-1)
-            ci = torch.cat([best_i, i], dim=-1)
-            best_s, sel = torch.topk(cs, min(k, cs.shape[-1]), dim=-1)
-            best_i = torch.gather(ci, -1, sel)
-    return best_s, best_i
+    return _chunked_topk(
+        lambda a, b: (qf @ db[a:b].to(torch.bfloat16).T).float(),
+        db.shape[0], k, row_base, allow, chunk_rows)
 
 
 def _knn_mfma(nat, db, q, k, row_base, allow=None, row_bias=None):
     """Fused MFMA score+topk over full BM-row panels + torch-scored tail."""
     qn = q.shape[0]
-    qq = q.to(torch.bfloat16)
-    if qn < 256:
-        qq = torch.cat(
-            [qq, torch.zeros(256 - qn, q.shape[1], dtype=torch.bfloat16, device=q.device)]
-        )
-    qq = qq.contiguous()
+    qb = q.to(torch.bfloat16)
     n = db.shape[0]
     bm = _knn_bm()
     n_main = (n // bm) * bm
     s, i = nat.knn_mfma(
-        db.narrow(0, 0, n_main), qq, row_base, k, allow,
-        None if row_bias is None else row_bias.narrow(0, 0, n_main), qn)
-    s, i = s[:qn], i[:qn]
-    if n_main < n:
-        tail = db.narrow(0, n_main, n - n_main)
+        db.narrow(0, 0, n_main), _pad_queries(qb).contiguous(), row_base, k,
+        allow, None if row_bias is None else row_bias.narrow(0, 0, n_main), qn)
+
+    def score_tail(a, b):
         if row_bias is None:
-            ts = (qq[:qn] @ tail.T).float()
-        else:
-            # fp32 product: the bf16 GEMM's rounded output would not survive
-            # the cancellation against the bias
-            ts = qq[:qn].float() @ tail.float().T + \
-                row_bias.narrow(0, n_main, n - n_main)
-        kk = min(k, n - n_main)
-        ok = None if allow is None else _mask_rows(allow, n_main, n)
-        bs, bi = _masked_topk(ts, ok, kk, row_base + n_main)
-        cs = torch.cat([s, bs], -1)
-        ci = torch.cat([i, bi], -1)
-        s, sel = torch.topk(cs, k, dim=-1)
-        i = torch.gather(ci, -1, sel)
-    return s, i
+            return (qb @ db[a:b].T).float()
+        # fp32 product: the bf16 GEMM's rounded output would not survive
+        # the cancellation against the bias
+        return qb.float() @ db[a:b].float().T + row_bias[a:b]
+
+    return _chunked_topk(score_tail, n, k, row_base, allow, start=n_main,
+                         best=(s[:qn], i[:qn]))
