@@ -4,10 +4,14 @@
 // vector_ops.hip
 void l2_normalize_(at::Tensor x);
 void fill_random_unit_(at::Tensor x, long long row_base, long long seed);
+
+// knn_gemv.hip
 std::tuple<at::Tensor, at::Tensor> knn_gemv(at::Tensor db, at::Tensor q,
                                             long long row_base, int k_out,
                                             c10::optional<at::Tensor> allow,
                                             c10::optional<at::Tensor> row_bias);
+
+// ivf_scan.hip
 std::tuple<at::Tensor, at::Tensor> ivf_scan(
     at::Tensor db, at::Tensor q, at::Tensor probes, at::Tensor list_off,
     at::Tensor list_rows, long long tail_start, long long max_len,
@@ -32,6 +36,16 @@ std::tuple<at::Tensor, at::Tensor> knn_mfma(at::Tensor db, at::Tensor q,
                                             c10::optional<at::Tensor> allow,
                                             c10::optional<at::Tensor> row_bias,
                                             int q_count);
+
+// knn_q8.hip
+long long knn_q8_bm_value();
+std::tuple<at::Tensor, at::Tensor> knn_fp8(at::Tensor db, at::Tensor q,
+                                           long long row_base, int k_out,
+                                           c10::optional<at::Tensor> allow);
+std::tuple<at::Tensor, at::Tensor> knn_i8(at::Tensor db, at::Tensor sa,
+                                          at::Tensor q, at::Tensor sq,
+                                          long long row_base, int k_out,
+                                          c10::optional<at::Tensor> allow);
 
 // gemm.hip
 at::Tensor gemm_nt(at::Tensor a, at::Tensor w, c10::optional<at::Tensor> bias,
@@ -71,7 +85,11 @@ at::Tensor add_layernorm(at::Tensor a, c10::optional<at::Tensor> b,
                          at::Tensor gamma, at::Tensor beta, double eps);
 at::Tensor bias_gelu(at::Tensor x, at::Tensor bias);
 at::Tensor mean_pool_l2norm(at::Tensor x, c10::optional<at::Tensor> mask);
+
+// flash_attn.hip
 at::Tensor flash_attn_nc(at::Tensor q, at::Tensor k, at::Tensor v);
+
+// decode_fused.hip
 void decode_step(at::Tensor layer_ptrs, at::Tensor x, at::Tensor q,
                  at::Tensor attn, at::Tensor h, at::Tensor rope_cos,
                  at::Tensor rope_sin, long long n_layers, long long hidden,
@@ -80,15 +98,6 @@ void decode_step(at::Tensor layer_ptrs, at::Tensor x, at::Tensor q,
                  long long pos);
 double sync_bench(long long iters, long long which, long long grid,
                   at::Tensor scratch);
-// knn_fp8.hip
-long long knn_q8_bm_value();
-std::tuple<at::Tensor, at::Tensor> knn_fp8(at::Tensor db, at::Tensor q,
-                                           long long row_base, int k_out,
-                                           c10::optional<at::Tensor> allow);
-std::tuple<at::Tensor, at::Tensor> knn_i8(at::Tensor db, at::Tensor sa,
-                                          at::Tensor q, at::Tensor sq,
-                                          long long row_base, int k_out,
-                                          c10::optional<at::Tensor> allow);
 void decode_tokens(at::Tensor layer_ptrs, at::Tensor x, at::Tensor q,
                    at::Tensor attn, at::Tensor h, at::Tensor rope_cos,
                    at::Tensor rope_sin, at::Tensor embed_w,

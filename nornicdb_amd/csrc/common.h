@@ -20,6 +20,8 @@ typedef short short8v __attribute__((ext_vector_type(8)));    // 16B: 8 x bf16
 typedef float float4v __attribute__((ext_vector_type(4)));    // 16B
 typedef float float2v __attribute__((ext_vector_type(2)));
 typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
+typedef unsigned int uint2v __attribute__((ext_vector_type(2)));   // 8B
+typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));  // fdot2 operand
 
 DEV_INLINE float bf16_bits_to_f32(unsigned short u) {
   union { unsigned int i; float f; } v;
@@ -97,9 +99,10 @@ DEV_INLINE float2v hash_gauss2(uint64_t key) {
   return r;
 }
 
-// 1-byte-per-element corpus formats of the quantised kNN and IVF kernels:
-// symmetric int8 with per-row scales, or OCP e4m3fn fp8.
-enum { Q8_FMT_I8 = 0, Q8_FMT_FP8 = 1 };
+// Corpus element formats. The quantised kNN kernel takes the two 1-byte
+// ones: symmetric int8 with per-row scales, or OCP e4m3fn fp8. The IVF scan
+// takes those and bf16.
+enum { Q8_FMT_I8 = 0, Q8_FMT_FP8 = 1, Q8_FMT_BF16 = 2 };
 
 #define HIP_CHECK_LAST()                                                    \
   do {                                                                      \

@@ -1,4 +1,5 @@
-// Fused MFMA score + top-k kNN over an FP8 (OCP e4m3fn) corpus.
+// Fused MFMA score + top-k kNN over a 1-byte-per-element corpus: k_knn_q8,
+// for FP8 (OCP e4m3fn) and symmetric int8 with per-row scales.
 //
 // Opt-in quantized search mode: the corpus is stored at 1 B/element —
 // HALF the HBM/LDS traffic of bf16 and 2x the per-GPU capacity (200M+

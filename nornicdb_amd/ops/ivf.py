@@ -7,10 +7,9 @@ numbers (`IVFLists.list_rows[list_off[c]:list_off[c + 1]]`), all below
 and are scanned by every query as one extra pseudo-list.
 
 Routes (`ivf_route_kind`), on the GPU with D % 128 == 0 and k <= 64:
-- bf16: the fused HIP kernel `ivf_scan` (csrc/vector_ops.hip) gathers,
+- bf16: the fused HIP kernel `ivf_scan` (csrc/ivf_scan.hip) gathers,
   scores and top-k's the probed rows;
-- int8 with per-row scales: `ivf_scan_i8`, the same block contract on
-  1-byte rows (exact int32 dot * sa[row] * sq[query]); the query is
+- int8 with per-row scales: `ivf_scan_i8`, the same kernel on 1-byte rows (exact int32 dot * sa[row] * sq[query]); the query is
   quantised in torch first, as `knn_search_int8` does;
 - fp8 e4m3: `ivf_scan_fp8`, fp32 accumulation of the converted bytes;
 - GPU otherwise (fp32 corpora, odd D, larger k): a torch gather fallback

@@ -42,7 +42,7 @@ def _knn_bm() -> int:
 
 def _knn_q8_bm() -> int:
     """Panel row count of the quantised (int8 / fp8) kernel, 96: the same
-    role as _knn_bm for csrc/knn_fp8.hip."""
+    role as _knn_bm for csrc/knn_q8.hip."""
     nat = native_or_none()
     return int(getattr(nat, "KNN_Q8_BM", 96)) if nat is not None else 96
 

@@ -39,7 +39,7 @@ class EmbeddingIndex:
         self.device = torch.device(device)
         # quant="fp8": store vectors as OCP e4m3fn — half the HBM traffic
         # and 2x capacity (200M+ 1024-d per 288 GB GPU), scored by the
-        # fp8 MFMA kernel (csrc/knn_fp8.hip); ~1% recall@10 cost on
+        # fp8 MFMA kernel (csrc/knn_q8.hip); ~1% recall@10 cost on
         # normalized vectors. No reference analogue (pkg/gpu is fp32).
         self.quant = quant
         if quant == "fp8":
@@ -205,22 +205,17 @@ class EmbeddingIndex:
         from ..ops import knn_search
 
         kk = min(k, self._n)
-        mask = self._allow_mask(allow_ids)
+        mask = self._allow_mask(allow_ids)     # None: the unfiltered route
+        db = self._buf[:self._n]
         if self.quant == "int8":
             from ..ops.knn import knn_search_int8
-            if mask is None:
-                return knn_search_int8(self._buf[:self._n],
-                                       self._scales[:self._n], q, kk)
-            return knn_search_int8(self._buf[:self._n],
-                                   self._scales[:self._n], q, kk, allow=mask)
-        if self._bias is not None:
-            s, i = knn_search(self._buf[:self._n], q.to(self.dtype), kk,
-                              allow=mask, row_bias=self._bias[:self._n])
-            return self._rescore_euclidean(q, i)
-        if mask is None:
-            return knn_search(self._buf[:self._n], q.to(self.dtype), kk)
-        return knn_search(self._buf[:self._n], q.to(self.dtype), kk,
-                          allow=mask)
+            return knn_search_int8(db, self._scales[:self._n], q, kk,
+                                   allow=mask)
+        if self._bias is None:
+            return knn_search(db, q.to(self.dtype), kk, allow=mask)
+        s, i = knn_search(db, q.to(self.dtype), kk, allow=mask,
+                          row_bias=self._bias[:self._n])
+        return self._rescore_euclidean(q, i)
 
     def _rescore_euclidean(self, q: torch.Tensor, i: torch.Tensor):
         """Exact scores for the slots a biased search returned: fp32
@@ -236,6 +231,18 @@ class EmbeddingIndex:
         score = (1.0 / (1.0 + dist)).masked_fill(i < 0, float("-inf"))
         return score, i
 
+    def _hits(self, scores, slots, k: int) -> List[Tuple[str, float]]:
+        """One query's (scores, slots) as [(id, score)]: the first k that
+        are neither unfilled (slot < 0) nor dead."""
+        out = []
+        for score, slot in zip(scores.tolist(), slots.tolist()):
+            if slot < 0 or slot in self._dead:
+                continue
+            out.append((self._ids[slot], float(score)))
+            if len(out) >= k:
+                break
+        return out
+
     def search(self, query, k: int,
                allow_ids: Optional[Iterable[str]] = None
                ) -> List[Tuple[str, float]]:
@@ -250,14 +257,7 @@ class EmbeddingIndex:
                                 device=self.device).reshape(1, -1)
             q = self._prep(q)
             s, i = self._knn(q, k, allow_ids)
-            out = []
-            for score, slot in zip(s[0].tolist(), i[0].tolist()):
-                if slot < 0 or slot in self._dead:
-                    continue
-                out.append((self._ids[slot], float(score)))
-                if len(out) >= k:
-                    break
-            return out
+            return self._hits(s[0], i[0], k)
 
     def search_batch(self, queries, k: int,
                      allow_ids: Optional[Iterable[str]] = None
@@ -269,17 +269,7 @@ class EmbeddingIndex:
                                 device=self.device)
             q = self._prep(q)
             s, i = self._knn(q, k, allow_ids)
-            outs = []
-            for r in range(q.shape[0]):
-                out = []
-                for score, slot in zip(s[r].tolist(), i[r].tolist()):
-                    if slot < 0 or slot in self._dead:
-                        continue
-                    out.append((self._ids[slot], float(score)))
-                    if len(out) >= k:
-                        break
-                outs.append(out)
-            return outs
+            return [self._hits(s[r], i[r], k) for r in range(q.shape[0])]
 
     def score_subset(self, query, ids: Sequence[str]) -> List[Tuple[str, float]]:
         """Exact re-scoring of a candidate subset (reference ScoreSubset)."""

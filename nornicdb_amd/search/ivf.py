@@ -111,23 +111,13 @@ class IVFIndex:
         n = emb._n
         lists = self._lists
         probes = ivf_route(lists, q, nprobe)
-        mask = emb._allow_mask(allow_ids)
-        if emb.quant == "int8":
-            return ivf_search(emb._buf[:n], q, min(k, n), lists, probes,
-                              lists.n_built, allow=mask,
-                              scales=emb._scales[:n])
-        return ivf_search(emb._buf[:n], q.to(emb.dtype), min(k, n), lists,
-                          probes, lists.n_built, allow=mask)
-
-    def _hits(self, scores, slots, k: int) -> List[Tuple[str, float]]:
-        out = []
-        for score, slot in zip(scores.tolist(), slots.tolist()):
-            if slot < 0 or slot in self.emb._dead:
-                continue
-            out.append((self.emb._ids[slot], float(score)))
-            if len(out) >= k:
-                break
-        return out
+        # int8 takes the float query (quantised behind ivf_search) and the
+        # row scales
+        int8 = emb.quant == "int8"
+        return ivf_search(emb._buf[:n], q if int8 else q.to(emb.dtype),
+                          min(k, n), lists, probes, lists.n_built,
+                          allow=emb._allow_mask(allow_ids),
+                          scales=emb._scales[:n] if int8 else None)
 
     def _delegates(self, nprobe: int) -> bool:
         return self._lists is None or nprobe >= self._lists.n_lists
@@ -148,7 +138,7 @@ class IVFIndex:
                                 device=self.emb.device).reshape(1, -1)
             q = self.emb._normalize(q)
             s, i = self._search(q, k, nprobe, allow_ids)
-            return self._hits(s[0], i[0], k)
+            return self.emb._hits(s[0], i[0], k)
 
     def search_batch(self, queries, k: int, nprobe: Optional[int] = None,
                      allow_ids: Optional[Iterable[str]] = None
@@ -163,4 +153,4 @@ class IVFIndex:
                                 device=self.emb.device)
             q = self.emb._normalize(q)
             s, i = self._search(q, k, nprobe, allow_ids)
-            return [self._hits(s[r], i[r], k) for r in range(q.shape[0])]
+            return [self.emb._hits(s[r], i[r], k) for r in range(q.shape[0])]

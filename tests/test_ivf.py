@@ -13,23 +13,13 @@ import torch
 from nornicdb_amd.ops import (IVFLists, ivf_build_lists, ivf_route,
                               ivf_search, ivf_search_exact, knn_search_exact,
                               pack_allow_mask)
+from nornicdb_amd.ops.ivf import _reachable
 from nornicdb_amd.ops.knn import quantize_fp8, quantize_int8
 from nornicdb_amd.search.kmeans import kmeans
 
-NEG_INF = float("-inf")
-
-
-def _py_reach(lists, probes, n, tail_start):
-    """bool [Q, n] from plain Python slices of the CSR arrays."""
-    off = lists.list_off.tolist()
-    rows = lists.list_rows.tolist()
-    reach = torch.zeros(probes.shape[0], n, dtype=torch.bool)
-    for qi, pr in enumerate(probes.tolist()):
-        for c in pr:
-            if 0 <= c < len(off) - 1:
-                reach[qi, rows[off[c]:off[c + 1]]] = True
-        reach[qi, tail_start:] = True
-    return reach
+from ivf_cases import (N, NEG_INF, ROW_BASE, TAILS, case_probes, check,
+                       clustered, cpu_lists, gpu_case, gpu_lists, py_reach,
+                       recall_at)
 
 
 # ---------------------------------------------------------------------------
@@ -103,7 +93,7 @@ def test_cpu_equals_exact_topk_over_masked_union():
     probes = torch.stack([torch.randperm(10, generator=g)[:3]
                           for _ in range(6)]).to(torch.int32)
     allow = torch.rand(n, generator=g) < 0.5
-    reach = _py_reach(lists, probes, n, n_built)
+    reach = py_reach(lists, probes, n, n_built)
     for mask in (None, allow, pack_allow_mask(allow)):
         ok = reach if mask is None else reach & allow
         ref = (q @ db.T).masked_fill(~ok, NEG_INF)
@@ -167,7 +157,7 @@ def test_cpu_int8_uses_row_scales():
     probes = torch.tensor([[0, 1]] * 4, dtype=torch.int32)
     qi, sq = quantize_int8(q)
     ref = (qi.float() * sq[:, None]) @ (db8.float() * sa[:, None]).T
-    ok = _py_reach(lists, probes, 300, 300)
+    ok = py_reach(lists, probes, 300, 300)
     rs, ri = torch.topk(ref.masked_fill(~ok, NEG_INF), 6, dim=-1)
     s, i = ivf_search(db8, q, 6, lists, probes, 300, scales=sa)
     assert torch.equal(i, ri) and torch.allclose(s, rs)
@@ -176,25 +166,6 @@ def test_cpu_int8_uses_row_scales():
 # ---------------------------------------------------------------------------
 # Recall floor on clustered data (a condition, not a measurement)
 # ---------------------------------------------------------------------------
-def clustered(seed, d, device="cpu", n=4096, n_centres=32, n_queries=64):
-    """Unit-norm fp32 rows around 32 random unit centres, and queries that
-    are perturbed rows."""
-    g = torch.Generator().manual_seed(seed)
-    nz = torch.nn.functional.normalize
-    centres = nz(torch.randn(n_centres, d, generator=g), dim=-1)
-    which = torch.randint(0, n_centres, (n,), generator=g)
-    x = nz(centres[which] + 0.15 * torch.randn(n, d, generator=g), dim=-1)
-    pick = torch.randperm(n, generator=g)[:n_queries]
-    q = nz(x[pick] + 0.05 * torch.randn(n_queries, d, generator=g), dim=-1)
-    return x.to(device), q.to(device)
-
-
-def recall_at(got_idx, ref_idx):
-    hits = sum(len(set(a) & set(b))
-               for a, b in zip(got_idx.tolist(), ref_idx.tolist()))
-    return hits / ref_idx.numel()
-
-
 @pytest.mark.parametrize("seed", [0, 1, 2])
 def test_cpu_recall_floor(seed):
     x, q = clustered(seed, 64)
@@ -212,15 +183,6 @@ def test_cpu_recall_floor(seed):
 # ---------------------------------------------------------------------------
 # GPU: ivf_scan kernel and the gather fallback
 # ---------------------------------------------------------------------------
-N = 3000
-C = 24
-ROW_BASE = 1000
-TAILS = [N, N - 1, N - 37]
-# list 0 empty, 1..4 around the 16-lane group count, 5 long enough that a
-# block strides through it several times at every Q below; the rest random
-FIXED = [0, 1, 15, 16, 17, 1200]
-AWKWARD = [0, 1, 2, 3, 4, 5]
-
 _cache = {}
 
 
@@ -235,106 +197,10 @@ def _corpus(d):
     return _cache[key]
 
 
-def _lists(tail_start):
-    """CSR over a random permutation of rows [0, tail_start): rows are in
-    random order inside every list. Returns (lists on GPU, lists on CPU)."""
-    key = ("lists", tail_start)
-    if key not in _cache:
-        g = torch.Generator().manual_seed(tail_start)
-        rest = tail_start - sum(FIXED)
-        cuts = torch.sort(torch.randint(0, rest + 1, (C - len(FIXED) - 1,),
-                                        generator=g)).values.tolist()
-        sizes = FIXED + [b - a for a, b in zip([0] + cuts, cuts + [rest])]
-        assert len(sizes) == C and sum(sizes) == tail_start
-        off = torch.zeros(C + 1, dtype=torch.int32)
-        off[1:] = torch.cumsum(torch.tensor(sizes), 0)
-        rows = torch.randperm(tail_start, generator=g).to(torch.int32)
-        cpu = IVFLists(torch.zeros(C, 8), off, rows, tail_start, max(sizes))
-        gpu = IVFLists(cpu.centroids.cuda(), off.cuda(), rows.cuda(),
-                       tail_start, max(sizes))
-        _cache[key] = (gpu, cpu)
-    return _cache[key]
-
-
-def _probes(q_count):
-    """int32 [Q, 8]: six distinct lists per query with two -1 entries mixed
-    in; query 0 probes the awkward lists, query 1 (if any) also carries an
-    out-of-range id."""
-    key = ("probes", q_count)
-    if key not in _cache:
-        g = torch.Generator().manual_seed(q_count)
-        out = torch.full((q_count, 8), -1, dtype=torch.int32)
-        for r in range(q_count):
-            cols = torch.randperm(8, generator=g)[:6]
-            pick = torch.tensor(AWKWARD) if r == 0 else \
-                torch.randperm(C, generator=g)[:6]
-            out[r, cols] = pick.to(torch.int32)
-        if q_count > 1:
-            out[1, (out[1] == -1).nonzero()[0, 0]] = C + 5
-        _cache[key] = out
-    return _cache[key]
-
-
 def _case(d, q_count, tail_start, masked):
-    """(q bf16 [Q, D], allow bool [N] or None, ok bool [Q, N]). Every query
-    copies a row it must not return: a row of a list it does not probe, or
-    (masked, odd queries) a disallowed row of a list it does probe."""
-    key = ("case", d, q_count, tail_start, masked)
-    if key in _cache:
-        return _cache[key]
-    db = _corpus(d)
-    _, cpu = _lists(tail_start)
-    probes = _probes(q_count)
-    reach = _py_reach(cpu, probes, N, tail_start)
-    g = torch.Generator().manual_seed(q_count * 7 + tail_start)
-    allow = None
-    if masked:
-        allow = torch.rand(N, generator=g) < 0.5
-    decoys = []
-    for r in range(q_count):
-        pool = (~reach[r]).nonzero().flatten()
-        if masked and r % 2 == 1:
-            pool = reach[r].nonzero().flatten()
-        row = int(pool[int(torch.randint(0, len(pool), (1,), generator=g))])
-        if masked:
-            allow[row] = False
-        decoys.append(row)
-    ok = reach if allow is None else reach & allow[None, :]
-    assert not ok[torch.arange(q_count), torch.tensor(decoys)].any()
-    q = db[torch.tensor(decoys).cuda()].clone()
-    out = (q, None if allow is None else allow.cuda(), ok.cuda())
-    _cache[key] = out
-    return out
-
-
-def _check(scores_fn, tol, q, ok, k, row_base, s, i):
-    """ok: bool [Q, N], the rows each query may return. scores_fn() is the
-    fp32 [Q, N] product of the stored values."""
-    torch.cuda.synchronize()
-    q_count, n = ok.shape
-    kk = min(k, n)
-    assert s.shape == (q_count, kk) and i.shape == s.shape
-    assert i.dtype == torch.int64 and s.dtype == torch.float32
-    ref = scores_fn().masked_fill(~ok, NEG_INF)
-    rs, _ = torch.topk(ref, kk, dim=-1)
-    m = ok.sum(-1).clamp_max(kk)
-    filled = torch.arange(kk, device=s.device)[None, :] < m[:, None]
-    assert ((i == -1) == ~filled).all(), i
-    assert (s[~filled] == NEG_INF).all(), s
-    loc = torch.where(filled, i - row_base, 0)
-    assert ((loc >= 0) & (loc < n)).all(), i
-    assert (torch.gather(ok, 1, loc) | ~filled).all(), \
-        "a row outside the probed, allowed set was returned"
-    srt = torch.where(filled, loc, -1 - torch.arange(kk, device=s.device)) \
-        .sort(dim=-1).values
-    assert (srt[:, 1:] != srt[:, :-1]).all(), "duplicate hit"
-    err = (s - rs)[filled].abs().max().item() if filled.any() else 0.0
-    own = (torch.gather(ref, 1, loc) - s)[filled].abs().max().item() \
-        if filled.any() else 0.0
-    print(f"Q={q_count} k={k}: rank err {err:.3e} own err {own:.3e}")
-    assert err <= tol, err
-    assert own <= tol, own
-    assert (s[:, :-1] >= s[:, 1:]).all()
+    """(q bf16 [Q, D], allow bool [N] or None, ok bool [Q, N]): every query
+    is a copy of its decoy row (ivf_cases.decoy_case)."""
+    return gpu_case(("bf16", d), _corpus(d), q_count, tail_start, masked)
 
 
 # atol of the gemv route's dot product on unit-norm rows
@@ -346,22 +212,21 @@ SCAN_TOL = 1e-2
 @pytest.mark.parametrize("masked", [False, True], ids=["nomask", "mask"])
 @pytest.mark.parametrize("k", [1, 10, 16, 17, 40, 64])
 @pytest.mark.parametrize("q_count", [1, 5, 17])
-@pytest.mark.parametrize("d", [128, 1024])
+@pytest.mark.parametrize("d", [128, 384, 1024])
 def test_gpu_scan_sweep(d, q_count, k, masked):
     db = _corpus(d)
-    probes = _probes(q_count).cuda()
+    probes = case_probes(q_count).cuda()
     for tail_start in TAILS:
-        lists, _ = _lists(tail_start)
+        lists, _ = gpu_lists(tail_start)
         q, allow, ok = _case(d, q_count, tail_start, masked)
         for row_base in (0, ROW_BASE):
             s, i = ivf_search(db, q, k, lists, probes, tail_start,
                               row_base=row_base, allow=allow)
-            _check(lambda: q.float() @ db.float().T, SCAN_TOL, q, ok, k,
-                   row_base, s, i)
+            check(q.float() @ db.float().T, SCAN_TOL, ok, k, row_base, s, i)
     # the oracle meets the same contract bit for bit on the same inputs
     es, ei = ivf_search_exact(db, q, k, lists, probes, tail_start,
                               row_base=ROW_BASE, allow=allow)
-    _check(lambda: q.float() @ db.float().T, 0.0, q, ok, k, ROW_BASE, es, ei)
+    check(q.float() @ db.float().T, 0.0, ok, k, ROW_BASE, es, ei)
     if masked:   # packed form of the mask
         s2, i2 = ivf_search(db, q, k, lists, probes, tail_start,
                             row_base=ROW_BASE, allow=pack_allow_mask(allow))
@@ -372,7 +237,7 @@ def test_gpu_scan_sweep(d, q_count, k, masked):
 @pytest.mark.parametrize("k", [16, 64])
 def test_gpu_scan_all_skipped(k):
     db = _corpus(128)
-    lists, _ = _lists(N)
+    lists, _ = gpu_lists(N)
     q = db[:5].contiguous()
     probes = torch.full((5, 4), -1, dtype=torch.int32, device="cuda")
     s, i = ivf_search(db, q, k, lists, probes, N, row_base=ROW_BASE)
@@ -383,7 +248,7 @@ def test_gpu_scan_all_skipped(k):
     none = torch.empty(5, 0, dtype=torch.int32, device="cuda")
     s, i = ivf_search(db, q, k, lists, none, N)
     assert (i == -1).all() and (s == NEG_INF).all()
-    lists37, _ = _lists(N - 37)
+    lists37, _ = gpu_lists(N - 37)
     s, i = ivf_search(db, q, k, lists37, none, N - 37)
     torch.cuda.synchronize()
     kk = min(k, 37)
@@ -396,7 +261,7 @@ def test_gpu_scan_all_skipped(k):
 @pytest.mark.gpu
 def test_gpu_scan_repeated_probe_scanned_once():
     db = _corpus(128)
-    lists, _ = _lists(N)
+    lists, _ = gpu_lists(N)
     q = db[:3].contiguous()
     once = torch.tensor([[5, 2, -1, -1]] * 3, dtype=torch.int32).cuda()
     twice = torch.tensor([[5, 2, 5, 2]] * 3, dtype=torch.int32).cuda()
@@ -405,6 +270,104 @@ def test_gpu_scan_repeated_probe_scanned_once():
     torch.cuda.synchronize()
     assert torch.equal(i1, i2) and torch.equal(s1, s2)
     assert (i1 >= 0).all()
+
+
+# ---------------------------------------------------------------------------
+# The bf16 and the fp8 scan against an exact reference, bit for bit. One
+# kernel text serves both element sizes; this is the guard on its address
+# arithmetic.
+#
+# Corpus and queries are k / 8 with k in -2..2: exact in bf16 and in e4m3.
+# Every product is a multiple of 1/64 of magnitude <= 4/64, so any partial
+# sum of up to 384 of them is an integer below 2^11 in units of 1/64: exact
+# in fp32 in whatever order it is taken. The fp32 matmul on the CPU is
+# therefore THE score, and both kernels must return it. int8 is left out:
+# 0.125 / (0.25 / 127) = 63.5 does not survive the rounding.
+# ---------------------------------------------------------------------------
+EXACT_DIMS = [128, 384]
+EXACT_Q, EXACT_K, EXACT_TAIL = 5, 10, N - 37
+
+
+def _exact_case(d, masked):
+    """CPU: (db fp32 [N, d], q fp32 [5, d], allow bool [N] or None, ref fp32
+    [5, N]): the exact scores, -inf outside the rows that
+    ivf_search_exact's reachability and the mask let a query return."""
+    key = ("exact", d, masked)
+    if key not in _cache:
+        g = torch.Generator().manual_seed(1000 + d)
+        db = torch.randint(-2, 3, (N, d), generator=g).float() / 8
+        q = torch.randint(-2, 3, (EXACT_Q, d), generator=g).float() / 8
+        allow = (torch.rand(N, generator=g) < 0.5) if masked else None
+        ok = _reachable(cpu_lists(EXACT_TAIL), case_probes(EXACT_Q), N,
+                        EXACT_TAIL)
+        if masked:
+            ok = ok & allow[None, :]
+        _cache[key] = (db, q, allow, (q @ db.T).masked_fill(~ok, NEG_INF))
+    return _cache[key]
+
+
+@pytest.mark.parametrize("d", EXACT_DIMS)
+def test_exact_reference(d):
+    """Conditions on the reference alone."""
+    db, q, _, ref = _exact_case(d, False)
+    for t in (db, q):       # the values survive both storage formats
+        assert torch.equal(t.to(torch.bfloat16).float(), t)
+        assert torch.equal(t.to(torch.float8_e4m3fn).float(), t)
+    fin = ref > NEG_INF
+    assert torch.equal(ref[fin].double(), (q.double() @ db.double().T)[fin])
+    # reachability agrees with the plain-Python one of the other tests
+    assert torch.equal(fin, py_reach(cpu_lists(EXACT_TAIL),
+                                     case_probes(EXACT_Q), N, EXACT_TAIL))
+    # unmasked, every query fills all k slots
+    assert (torch.topk(ref, EXACT_K, dim=-1).values > NEG_INF).all()
+    _, _, allow, mref = _exact_case(d, True)
+    assert ((mref > NEG_INF) == (fin & allow[None, :])).all()
+
+
+def _check_exact(s, i, ref, row_base):
+    """(s, i) against the exact scores ref [Q, n] (-inf where a row is
+    unreachable or disallowed). Scores tie often: nothing is asserted about
+    which of several tied rows comes back."""
+    k = s.shape[1]
+    s_ref = torch.topk(ref, k, dim=-1).values
+    assert s.shape == s_ref.shape and i.shape == s_ref.shape
+    assert s.dtype == torch.float32 and i.dtype == torch.int64
+    assert torch.equal(s, s_ref), (s != s_ref).nonzero()[:8]
+    filled = s_ref > NEG_INF
+    assert ((i >= 0) == filled).all()
+    assert (i[~filled] == -1).all()
+    loc = (i - row_base).clamp_min(0)
+    assert ((i - row_base >= 0) | ~filled).all() and (loc < ref.shape[1]).all()
+    # reachable, allowed, and scored exactly what was returned
+    assert (torch.gather(ref, 1, loc) == s)[filled].all()
+    assert (torch.gather(ref, 1, loc) > NEG_INF)[filled].all()
+    srt = torch.sort(torch.where(filled, i, -1 - torch.arange(
+        k, device=i.device).expand_as(i)), dim=-1).values
+    assert (srt[:, 1:] != srt[:, :-1]).all(), "duplicate hit"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("masked", [False, True], ids=["nomask", "mask"])
+@pytest.mark.parametrize("d", EXACT_DIMS)
+def test_gpu_scan_exact_across_formats(monkeypatch, d, masked):
+    from nornicdb_amd.ops import ivf as ivf_ops
+
+    def boom(*a, **kw):
+        raise AssertionError("the torch gather route was taken")
+    monkeypatch.setattr(ivf_ops, "_ivf_gather", boom)
+    db, q, allow, ref = (None if t is None else t.cuda()
+                         for t in _exact_case(d, masked))
+    lists, _ = gpu_lists(EXACT_TAIL)
+    probes = case_probes(EXACT_Q).cuda()
+    got = {}
+    for fmt, stored in (("bf16", db.to(torch.bfloat16)),
+                        ("fp8", quantize_fp8(db))):
+        s, i = ivf_search(stored, q, EXACT_K, lists, probes, EXACT_TAIL,
+                          row_base=ROW_BASE, allow=allow)
+        torch.cuda.synchronize()
+        _check_exact(s, i, ref, ROW_BASE)
+        got[fmt] = s
+    assert torch.equal(got["bf16"], got["fp8"])
 
 
 # Both sides are fp32 products of the same stored values; they differ only
@@ -419,8 +382,8 @@ def test_gpu_fallback_contract(kind):
     tail_start = N - 37
     d = 96 if kind == "bf16-d96" else 128
     k = 100 if kind == "bf16-k100" else 10
-    lists, _ = _lists(tail_start)
-    probes = _probes(5).cuda()
+    lists, _ = gpu_lists(tail_start)
+    probes = case_probes(5).cuda()
     if d == 128:
         q, allow, ok = _case(128, 5, tail_start, True)
         base = _corpus(128)
@@ -445,7 +408,7 @@ def test_gpu_fallback_contract(kind):
         st, qv, vals = base, q.float(), base.float()
     s, i = ivf_search(st, q, k, lists, probes, tail_start, row_base=ROW_BASE,
                       allow=allow, scales=scales)
-    _check(lambda: qv @ vals.T, FALLBACK_TOL, q, ok, k, ROW_BASE, s, i)
+    check(qv @ vals.T, FALLBACK_TOL, ok, k, ROW_BASE, s, i)
 
 
 @pytest.mark.gpu
@@ -453,9 +416,9 @@ def test_gpu_wrapper_rejects_bad_arguments():
     from nornicdb_amd.ops import require_native
     nat = require_native()
     db = _corpus(128)
-    lists, cpu = _lists(N)
+    lists, cpu = gpu_lists(N)
     q = db[:2].contiguous()
-    pr = _probes(2).cuda()
+    pr = case_probes(2).cuda()
     good = (db, q, pr, lists.list_off, lists.list_rows, N, lists.max_len, 0,
             10, None)
     s, i = nat.ivf_scan(*good)

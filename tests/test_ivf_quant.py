@@ -14,13 +14,14 @@ import numpy as np
 import pytest
 import torch
 
-from nornicdb_amd.ops import (IVFLists, ivf_build_lists, ivf_route,
-                              ivf_search, ivf_search_exact, pack_allow_mask)
+from nornicdb_amd.ops import (ivf_build_lists, ivf_route, ivf_search,
+                              ivf_search_exact, pack_allow_mask)
 from nornicdb_amd.ops import ivf as ivf_ops
 from nornicdb_amd.ops.knn import quantize_fp8, quantize_int8
 from nornicdb_amd.search.kmeans import kmeans
 
-NEG_INF = float("-inf")
+from ivf_cases import (N, NEG_INF, ROW_BASE, TAILS, check, clustered,
+                       gpu_case, gpu_lists, case_probes, recall_at)
 
 
 # ---------------------------------------------------------------------------
@@ -49,15 +50,6 @@ def test_route_kind_table(dtype, d, k):
 # vector times a factor from {0.5, 1, 2}, so int8 row scales spread about
 # 7x and query scales differ from query to query.
 # ---------------------------------------------------------------------------
-N = 3000
-C = 24
-ROW_BASE = 1000
-TAILS = [N, N - 1, N - 37]
-# list 0 empty, 1..4 around the 16-lane group count, 5 long enough that a
-# block strides through it several times at every Q below; the rest random
-FIXED = [0, 1, 15, 16, 17, 1200]
-AWKWARD = [0, 1, 2, 3, 4, 5]
-
 # Kernel and oracle are fp32 products of the same stored values; they differ
 # in summation order only (the int32 dot is exact and converts to fp32
 # exactly for D * 127^2 < 2^24): D * 2^-24 * |q||x| with |q||x| <= 4 and
@@ -65,19 +57,6 @@ AWKWARD = [0, 1, 2, 3, 4, 5]
 TOL = 4e-4
 
 _cache = {}
-
-
-def _py_reach(lists, probes, n, tail_start):
-    """bool [Q, n] from plain Python slices of the CSR arrays."""
-    off = lists.list_off.tolist()
-    rows = lists.list_rows.tolist()
-    reach = torch.zeros(probes.shape[0], n, dtype=torch.bool)
-    for qi, pr in enumerate(probes.tolist()):
-        for c in pr:
-            if 0 <= c < len(off) - 1:
-                reach[qi, rows[off[c]:off[c + 1]]] = True
-        reach[qi, tail_start:] = True
-    return reach
 
 
 def _base(d):
@@ -113,105 +92,10 @@ def _query_values(fmt, q):
     return q.to(torch.float8_e4m3fn).float()
 
 
-def _lists(tail_start):
-    """CSR over a random permutation of rows [0, tail_start): rows are in
-    random order inside every list. Returns (lists on GPU, lists on CPU)."""
-    key = ("lists", tail_start)
-    if key not in _cache:
-        g = torch.Generator().manual_seed(tail_start)
-        rest = tail_start - sum(FIXED)
-        cuts = torch.sort(torch.randint(0, rest + 1, (C - len(FIXED) - 1,),
-                                        generator=g)).values.tolist()
-        sizes = FIXED + [b - a for a, b in zip([0] + cuts, cuts + [rest])]
-        assert len(sizes) == C and sum(sizes) == tail_start
-        off = torch.zeros(C + 1, dtype=torch.int32)
-        off[1:] = torch.cumsum(torch.tensor(sizes), 0)
-        rows = torch.randperm(tail_start, generator=g).to(torch.int32)
-        cpu = IVFLists(torch.zeros(C, 8), off, rows, tail_start, max(sizes))
-        gpu = IVFLists(cpu.centroids.cuda(), off.cuda(), rows.cuda(),
-                       tail_start, max(sizes))
-        _cache[key] = (gpu, cpu)
-    return _cache[key]
-
-
-def _probes(q_count):
-    """int32 [Q, 8]: six distinct lists per query with two -1 entries mixed
-    in; query 0 probes the awkward lists, query 1 (if any) also carries an
-    out-of-range id."""
-    key = ("probes", q_count)
-    if key not in _cache:
-        g = torch.Generator().manual_seed(q_count)
-        out = torch.full((q_count, 8), -1, dtype=torch.int32)
-        for r in range(q_count):
-            cols = torch.randperm(8, generator=g)[:6]
-            pick = torch.tensor(AWKWARD) if r == 0 else \
-                torch.randperm(C, generator=g)[:6]
-            out[r, cols] = pick.to(torch.int32)
-        if q_count > 1:
-            out[1, (out[1] == -1).nonzero()[0, 0]] = C + 5
-        _cache[key] = out
-    return _cache[key]
-
-
 def _case(d, q_count, tail_start, masked):
-    """(q fp32 [Q, D], allow bool [N] or None, ok bool [Q, N]). Every query
-    copies a row it must not return: a row of a list it does not probe, or
-    (masked, odd queries) a disallowed row of a list it does probe."""
-    key = ("case", d, q_count, tail_start, masked)
-    if key in _cache:
-        return _cache[key]
-    _, cpu = _lists(tail_start)
-    probes = _probes(q_count)
-    reach = _py_reach(cpu, probes, N, tail_start)
-    g = torch.Generator().manual_seed(q_count * 7 + tail_start)
-    allow = None
-    if masked:
-        allow = torch.rand(N, generator=g) < 0.5
-    decoys = []
-    for r in range(q_count):
-        pool = (~reach[r]).nonzero().flatten()
-        if masked and r % 2 == 1:
-            pool = reach[r].nonzero().flatten()
-        row = int(pool[int(torch.randint(0, len(pool), (1,), generator=g))])
-        if masked:
-            allow[row] = False
-        decoys.append(row)
-    ok = reach if allow is None else reach & allow[None, :]
-    assert not ok[torch.arange(q_count), torch.tensor(decoys)].any()
-    q = _base(d)[torch.tensor(decoys).cuda()].clone()
-    out = (q, None if allow is None else allow.cuda(), ok.cuda())
-    _cache[key] = out
-    return out
-
-
-def _check(ref_scores, tol, ok, k, row_base, s, i):
-    """ok: bool [Q, N], the rows each query may return. ref_scores is the
-    fp32 [Q, N] product of the stored values."""
-    torch.cuda.synchronize()
-    q_count, n = ok.shape
-    kk = min(k, n)
-    assert s.shape == (q_count, kk) and i.shape == s.shape
-    assert i.dtype == torch.int64 and s.dtype == torch.float32
-    ref = ref_scores.masked_fill(~ok, NEG_INF)
-    rs, _ = torch.topk(ref, kk, dim=-1)
-    m = ok.sum(-1).clamp_max(kk)
-    filled = torch.arange(kk, device=s.device)[None, :] < m[:, None]
-    assert ((i == -1) == ~filled).all(), i
-    assert (s[~filled] == NEG_INF).all(), s
-    loc = torch.where(filled, i - row_base, 0)
-    assert ((loc >= 0) & (loc < n)).all(), i
-    assert (torch.gather(ok, 1, loc) | ~filled).all(), \
-        "a row outside the probed, allowed set was returned"
-    srt = torch.where(filled, loc, -1 - torch.arange(kk, device=s.device)) \
-        .sort(dim=-1).values
-    assert (srt[:, 1:] != srt[:, :-1]).all(), "duplicate hit"
-    err = (s - rs)[filled].abs().max().item() if filled.any() else 0.0
-    own = (torch.gather(ref, 1, loc) - s)[filled].abs().max().item() \
-        if filled.any() else 0.0
-    print(f"Q={q_count} k={k}: rank err {err:.3e} own err {own:.3e}")
-    assert err <= tol, err
-    assert own <= tol, own
-    assert (s[:, :-1] >= s[:, 1:]).all()
+    """(q fp32 [Q, D], allow bool [N] or None, ok bool [Q, N]): every query
+    is a copy of its decoy row (ivf_cases.decoy_case)."""
+    return gpu_case(("base", d), _base(d), q_count, tail_start, masked)
 
 
 def _forbid_gather(monkeypatch):
@@ -232,20 +116,20 @@ def _forbid_gather(monkeypatch):
 def test_gpu_quant_scan_sweep(monkeypatch, fmt, d, q_count, k, masked):
     _forbid_gather(monkeypatch)
     db, scales, vals = _stored(fmt, d)
-    probes = _probes(q_count).cuda()
+    probes = case_probes(q_count).cuda()
     for tail_start in TAILS:
-        lists, _ = _lists(tail_start)
+        lists, _ = gpu_lists(tail_start)
         q, allow, ok = _case(d, q_count, tail_start, masked)
         ref = _query_values(fmt, q) @ vals.T
         for row_base in (0, ROW_BASE):
             s, i = ivf_search(db, q, k, lists, probes, tail_start,
                               row_base=row_base, allow=allow, scales=scales)
-            _check(ref, TOL, ok, k, row_base, s, i)
+            check(ref, TOL, ok, k, row_base, s, i)
         # against the oracle itself, slot by slot
         es, ei = ivf_search_exact(db, q, k, lists, probes, tail_start,
                                   row_base=ROW_BASE, allow=allow,
                                   scales=scales)
-        _check(ref, 0.0, ok, k, ROW_BASE, es, ei)
+        check(ref, 0.0, ok, k, ROW_BASE, es, ei)
         assert torch.equal(i == -1, ei == -1)
         fin = ei >= 0
         gap = (s - es)[fin].abs().max().item() if fin.any() else 0.0
@@ -265,11 +149,11 @@ def test_gpu_quant_takes_the_kernel_route(monkeypatch, fmt, k):
     _forbid_gather(monkeypatch)
     tail_start = N - 37
     db, scales, vals = _stored(fmt, 128)
-    lists, _ = _lists(tail_start)
+    lists, _ = gpu_lists(tail_start)
     q, allow, ok = _case(128, 5, tail_start, True)
-    s, i = ivf_search(db, q, k, lists, _probes(5).cuda(), tail_start,
+    s, i = ivf_search(db, q, k, lists, case_probes(5).cuda(), tail_start,
                       row_base=ROW_BASE, allow=allow, scales=scales)
-    _check(_query_values(fmt, q) @ vals.T, TOL, ok, k, ROW_BASE, s, i)
+    check(_query_values(fmt, q) @ vals.T, TOL, ok, k, ROW_BASE, s, i)
 
 
 @pytest.mark.gpu
@@ -278,7 +162,7 @@ def test_gpu_quant_takes_the_kernel_route(monkeypatch, fmt, k):
 def test_gpu_quant_all_skipped(monkeypatch, fmt, k):
     _forbid_gather(monkeypatch)
     db, scales, _ = _stored(fmt, 128)
-    lists, _ = _lists(N)
+    lists, _ = gpu_lists(N)
     q = _base(128)[:5].contiguous()
     probes = torch.full((5, 4), -1, dtype=torch.int32, device="cuda")
     s, i = ivf_search(db, q, k, lists, probes, N, row_base=ROW_BASE,
@@ -290,7 +174,7 @@ def test_gpu_quant_all_skipped(monkeypatch, fmt, k):
     none = torch.empty(5, 0, dtype=torch.int32, device="cuda")
     s, i = ivf_search(db, q, k, lists, none, N, scales=scales)
     assert (i == -1).all() and (s == NEG_INF).all()
-    lists37, _ = _lists(N - 37)
+    lists37, _ = gpu_lists(N - 37)
     s, i = ivf_search(db, q, k, lists37, none, N - 37, scales=scales)
     torch.cuda.synchronize()
     kk = min(k, 37)
@@ -305,7 +189,7 @@ def test_gpu_quant_all_skipped(monkeypatch, fmt, k):
 def test_gpu_quant_repeated_probe_scanned_once(monkeypatch, fmt):
     _forbid_gather(monkeypatch)
     db, scales, _ = _stored(fmt, 128)
-    lists, _ = _lists(N)
+    lists, _ = gpu_lists(N)
     q = _base(128)[:3].contiguous()
     once = torch.tensor([[5, 2, -1, -1]] * 3, dtype=torch.int32).cuda()
     twice = torch.tensor([[5, 2, 5, 2]] * 3, dtype=torch.int32).cuda()
@@ -323,9 +207,9 @@ def test_gpu_int8_is_deterministic(monkeypatch, k):
     _forbid_gather(monkeypatch)
     tail_start = N - 37
     db, scales, _ = _stored("int8", 1024)
-    lists, _ = _lists(tail_start)
+    lists, _ = gpu_lists(tail_start)
     q, allow, _ = _case(1024, 17, tail_start, True)
-    probes = _probes(17).cuda()
+    probes = case_probes(17).cuda()
     a = ivf_search(db, q, k, lists, probes, tail_start, allow=allow,
                    scales=scales)
     b = ivf_search(db, q, k, lists, probes, tail_start, allow=allow,
@@ -340,8 +224,8 @@ def test_gpu_quant_wrapper_rejects_bad_arguments(fmt):
     from nornicdb_amd.ops import require_native
     nat = require_native()
     st, scales, _ = _stored(fmt, 128)
-    lists, cpu = _lists(N)
-    pr = _probes(2).cuda()
+    lists, cpu = gpu_lists(N)
+    pr = case_probes(2).cuda()
     qf = _base(128)[:2].contiguous()
     tail = {"probes": pr, "list_off": lists.list_off,
             "list_rows": lists.list_rows, "tail_start": N,
@@ -392,25 +276,6 @@ def test_gpu_quant_wrapper_rejects_bad_arguments(fmt):
 # ---------------------------------------------------------------------------
 # GPU: index level
 # ---------------------------------------------------------------------------
-def clustered(seed, d, device="cpu", n=4096, n_centres=32, n_queries=64):
-    """Unit-norm fp32 rows around 32 random unit centres, and queries that
-    are perturbed rows."""
-    g = torch.Generator().manual_seed(seed)
-    nz = torch.nn.functional.normalize
-    centres = nz(torch.randn(n_centres, d, generator=g), dim=-1)
-    which = torch.randint(0, n_centres, (n,), generator=g)
-    x = nz(centres[which] + 0.15 * torch.randn(n, d, generator=g), dim=-1)
-    pick = torch.randperm(n, generator=g)[:n_queries]
-    q = nz(x[pick] + 0.05 * torch.randn(n_queries, d, generator=g), dim=-1)
-    return x.to(device), q.to(device)
-
-
-def recall_at(got_idx, ref_idx):
-    hits = sum(len(set(a) & set(b))
-               for a, b in zip(got_idx.tolist(), ref_idx.tolist()))
-    return hits / ref_idx.numel()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("quant", ["int8", "fp8"])
 def test_gpu_quant_index_level(monkeypatch, quant):

@@ -119,7 +119,8 @@ def test_index_no_mask_without_tombstones_or_filter(monkeypatch):
     monkeypatch.setattr(ops_mod, "knn_search", spy)
     assert idx.search(np.eye(3, 16)[1], 2)[0][0] == "b"
     (args, kw), = calls
-    assert len(args) == 3 and not kw        # exactly the unfiltered call
+    # exactly the unfiltered call: (db, q, k), nothing else but allow=None
+    assert len(args) == 3 and set(kw) <= {"allow"} and kw.get("allow") is None
 
 
 # ---------------------------------------------------------------------------
