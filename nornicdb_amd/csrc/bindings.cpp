@@ -26,6 +26,13 @@ std::tuple<at::Tensor, at::Tensor> ivf_scan_fp8(
     at::Tensor list_rows, long long tail_start, long long max_len,
     long long row_base, int k_out, c10::optional<at::Tensor> allow);
 
+// bm25_scan.hip
+long long bm25_range_value();
+std::tuple<at::Tensor, at::Tensor> bm25_scan(
+    at::Tensor post_off, at::Tensor post_doc, at::Tensor post_tf,
+    at::Tensor doc_len, at::Tensor q_terms, at::Tensor q_w, double c0,
+    double c1, int k_out, c10::optional<at::Tensor> allow);
+
 // knn_mfma.hip
 long long knn_bm_value();
 long long knn_rg_value();
@@ -142,6 +149,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("db"), py::arg("q"), py::arg("probes"), py::arg("list_off"),
         py::arg("list_rows"), py::arg("tail_start"), py::arg("max_len"),
         py::arg("row_base") = 0, py::arg("k_out") = 10,
+        py::arg("allow") = c10::nullopt);
+  // BM25_RANGE: documents per LDS accumulator range of bm25_scan
+  m.attr("BM25_RANGE") = bm25_range_value();
+  m.def("bm25_scan", &bm25_scan,
+        "BM25 posting-list scan: fused posting gather + score + top-k "
+        "(k <= 64) over CSR postings; a posting adds w*tf/(tf+c0+c1*dl) to "
+        "its document, only documents with a score > 0 are returned",
+        py::arg("post_off"), py::arg("post_doc"), py::arg("post_tf"),
+        py::arg("doc_len"), py::arg("q_terms"), py::arg("q_w"),
+        py::arg("c0"), py::arg("c1"), py::arg("k_out") = 10,
         py::arg("allow") = c10::nullopt);
   // KNN_BM: rows of one kNN panel; KNN_RG: row groups the panel is made of
   m.attr("KNN_BM") = KNN_BM_VALUE;

@@ -45,3 +45,6 @@ from .ivf import (  # noqa: E402,F401
     IVFLists, ivf_build_lists, ivf_route, ivf_route_kind, ivf_search,
     ivf_search_exact,
 )
+from .bm25 import (  # noqa: E402,F401
+    BM25Postings, bm25_build_postings, bm25_search, bm25_search_exact,
+)

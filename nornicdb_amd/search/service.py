@@ -16,6 +16,7 @@ import numpy as np
 
 from ..storage.types import Engine, EventType, Node
 from .bm25 import FulltextIndex
+from .bm25_device import DeviceFulltextIndex
 from .embedding_index import EmbeddingIndex
 from .fusion import mmr_diversify, rrf_fuse
 from .hnsw import HNSWIndex
@@ -47,7 +48,7 @@ class SearchService:
     def __init__(self, engine: Engine, dims: int = 1024,
                  device: Optional[str] = None, use_hnsw: bool = True,
                  embedder=None, quant: Optional[str] = None,
-                 ivf: bool = False):
+                 ivf: bool = False, fulltext_gpu: bool = False):
         self.engine = engine
         self.dims = dims
         self.embedder = embedder
@@ -68,6 +69,14 @@ class SearchService:
         # corpora (or any query that passes nprobe) to them
         ivf = ivf or _os.environ.get("NORNICDB_SEARCH_IVF") == "1"
         self.ivf = IVFIndex(self.emb) if ivf else None
+        # opt-in device-resident BM25 (fulltext_gpu=True or
+        # NORNICDB_SEARCH_FULLTEXT_GPU=1): build_indexes() freezes the
+        # postings on the device, text queries are scored there, and
+        # recluster() rebuilds them once enough documents have changed
+        fulltext_gpu = fulltext_gpu or \
+            _os.environ.get("NORNICDB_SEARCH_FULLTEXT_GPU") == "1"
+        self.fulltext_dev = (DeviceFulltextIndex(self.fulltext, device=device)
+                             if fulltext_gpu else None)
         self.pipeline = VectorSearchPipeline(self.emb, self.hnsw,
                                              self.clusters, ivf=self.ivf)
         # label -> ids of nodes with an embedding; the vector path turns a
@@ -140,8 +149,12 @@ class SearchService:
         """Full scan (reference BuildIndexes)."""
         for node in self.engine.all_nodes():
             self.index_node(node)
+        if self.fulltext_dev is not None:
+            self.fulltext_dev.build()
 
     def recluster(self, k: int = None):
+        if self.fulltext_dev is not None and self.fulltext_dev.needs_rebuild():
+            self.fulltext_dev.build()
         ids = self.emb.ids()
         if not ids:
             return
@@ -163,9 +176,16 @@ class SearchService:
                                     nprobe=nprobe)
         return self._materialize(hits, k, labels, source="vector")
 
+    def _fulltext_search(self, query: str, k: int):
+        """BM25 hits from the device index when it is enabled (it
+        delegates to the host index until it is built)."""
+        ft = self.fulltext_dev if self.fulltext_dev is not None \
+            else self.fulltext
+        return ft.search(query, k)
+
     def text_search(self, query: str, k: int = 10,
                     labels: Sequence[str] = None) -> List[SearchResult]:
-        hits = self.fulltext.search(query, k * 3 if labels else k)
+        hits = self._fulltext_search(query, k * 3 if labels else k)
         return self._materialize(hits, k, labels, source="fulltext")
 
     def search(self, query: str = None, query_vec=None, k: int = 10,
@@ -178,7 +198,7 @@ class SearchService:
             query_vec = self.embedder.embed_query(query)
         rankings = []
         if query:
-            rankings.append(self.fulltext.search(query, max(k * 4, 40)))
+            rankings.append(self._fulltext_search(query, max(k * 4, 40)))
         if query_vec is not None and len(self.emb) > 0:
             rankings.append(self.pipeline.search(
                 np.asarray(query_vec, np.float32), max(k * 4, 40),
