@@ -57,6 +57,7 @@ std::tuple<at::Tensor, at::Tensor> knn_i8(at::Tensor db, at::Tensor sa,
 // gemm.hip
 at::Tensor gemm_nt(at::Tensor a, at::Tensor w, c10::optional<at::Tensor> bias,
                    long long act);
+long long gemm_nt_variant(long long M);
 
 // kmeans.hip
 std::tuple<at::Tensor, at::Tensor> kmeans_assign(at::Tensor x, at::Tensor cent,
@@ -174,9 +175,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k_out") = 10, py::arg("allow") = c10::nullopt,
         py::arg("row_bias") = c10::nullopt, py::arg("q_count") = 256);
   m.def("gemm_nt", &gemm_nt,
-        "C = A[M,K] @ W[N,K]^T + bias (+GELU), bf16 MFMA 256x256 8-phase",
+        "C = A[M,K] @ W[N,K]^T + bias (+GELU), bf16 MFMA; kernel per "
+        "gemm_nt_variant(M)",
         py::arg("a"), py::arg("w"), py::arg("bias") = c10::nullopt,
         py::arg("act") = 0);
+  m.def("gemm_nt_variant", &gemm_nt_variant,
+        "row tile (96 or 256) of the kernel gemm_nt launches for M rows, "
+        "NORNICDB_GEMM_KERNEL honoured as in the launch",
+        py::arg("m"));
   m.def("add_layernorm", &add_layernorm, "LN(a+b)*gamma+beta fused (bf16)",
         py::arg("a"), py::arg("b"), py::arg("gamma"), py::arg("beta"),
         py::arg("eps") = 1e-5);
@@ -224,7 +230,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scratch"));
   m.def("kmeans_assign", &kmeans_assign,
         "fused distance+argmin assignment (bf16 x/centroids)");
-  m.def("kmeans_accum", &kmeans_accum, "atomic centroid accumulate");
+  m.def("kmeans_accum", &kmeans_accum,
+        "atomic centroid accumulate. assign values must lie in [0, k): the "
+        "wrapper cannot check them without a device sync, and a value "
+        "outside is an out-of-bounds write");
   m.def("kmeans_finalize", &kmeans_finalize,
         "sums/counts -> centroids + drift^2 (empty keep old)");
   m.def("kmeanspp_update", &kmeanspp_update,

@@ -51,7 +51,43 @@ __global__ void k_add_layernorm(const unsigned short* __restrict__ a,
     sum = wave_reduce_sum(sum);
     sq = wave_reduce_sum(sq);
     float mean = sum / d;
-    float inv = rsqrtf(fmaxf(sq / d - mean * mean, 0.f) + eps);
+    float var = sq / d - mean * mean;
+    // A row far from zero (|mean| > 2 std) loses the variance in
+    // E[x^2] - mean^2, and the mean its last digits. Such a row is summed
+    // again as x - x[0], and the shift is kept apart from the then small
+    // mean. x - x[0] is exact where the two are within a factor of 2 of
+    // each other (Sterbenz), which is where the cancellation is; elsewhere
+    // it is rounded once, to 2^-24 of a difference of std size, not of mean
+    // size. Every other row
+    // keeps the single pass and its arithmetic. The condition is the same
+    // in all lanes, is true for a negative var (NaN root), and does not
+    // use mean * mean, so that the product above has one use and stays
+    // fused into var.
+    float shift = 0.f;
+    if (!(fabsf(mean) <= 2.f * sqrtf(var))) {
+      shift = bf16_bits_to_f32(pa[0]);
+      if (pb) shift += bf16_bits_to_f32(pb[0]);
+      sum = 0.f;
+      sq = 0.f;
+      for (int c = lane * 8; c < d; c += WAVE * 8) {
+        short8v va = *reinterpret_cast<const short8v*>(pa + c);
+        short8v vb;
+        if (pb) vb = *reinterpret_cast<const short8v*>(pb + c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float f = bf16_bits_to_f32((unsigned short)va[j]);
+          if (pb) f += bf16_bits_to_f32((unsigned short)vb[j]);
+          f -= shift;
+          sum += f;
+          sq += f * f;
+        }
+      }
+      sum = wave_reduce_sum(sum);
+      sq = wave_reduce_sum(sq);
+      mean = sum / d;  // of the shifted row
+      var = sq / d - mean * mean;
+    }
+    float inv = rsqrtf(fmaxf(var, 0.f) + eps);
     unsigned short* py = y + row * d;
     for (int c = lane * 8; c < d; c += WAVE * 8) {
       short8v va = *reinterpret_cast<const short8v*>(pa + c);
@@ -66,7 +102,7 @@ __global__ void k_add_layernorm(const unsigned short* __restrict__ a,
         if (pb) f += bf16_bits_to_f32((unsigned short)vb[j]);
         float g = bf16_bits_to_f32((unsigned short)vg[j]);
         float be = bf16_bits_to_f32((unsigned short)vbe[j]);
-        o[j] = (short)f32_to_bf16_bits((f - mean) * inv * g + be);
+        o[j] = (short)f32_to_bf16_bits(((f - shift) - mean) * inv * g + be);
       }
       *reinterpret_cast<short8v*>(py + c) = o;
     }
@@ -153,17 +189,25 @@ at::Tensor add_layernorm(at::Tensor a, c10::optional<at::Tensor> b,
                          at::Tensor gamma, at::Tensor beta, double eps) {
   TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16);
   auto a2 = a.contiguous();
+  TORCH_CHECK(a2.dim() >= 1 && a2.size(-1) > 0 && a2.size(-1) % 8 == 0 &&
+                  a2.size(-1) <= 8192,
+              "add_layernorm: D % 8 == 0, 0 < D <= 8192");
   long long rows = a2.numel() / a2.size(-1);
   int d = (int)a2.size(-1);
-  TORCH_CHECK(d % 8 == 0 && d <= 8192, "add_layernorm: D % 8 == 0, D <= 8192");
   at::Tensor y = at::empty_like(a2);
   const unsigned short* bp = nullptr;
   at::Tensor bc;
   if (b.has_value()) {
     bc = b->contiguous();
-    TORCH_CHECK(bc.sizes() == a2.sizes());
+    TORCH_CHECK(bc.is_cuda() && bc.scalar_type() == at::kBFloat16 &&
+                    bc.sizes() == a2.sizes(),
+                "add_layernorm: b must be bf16 CUDA of a's shape");
     bp = (const unsigned short*)bc.data_ptr();
   }
+  TORCH_CHECK(gamma.is_cuda() && beta.is_cuda() && gamma.numel() == d &&
+                  beta.numel() == d,
+              "add_layernorm: gamma and beta must be CUDA [D]");
+  if (rows == 0) return y.view(a.sizes());
   auto g = gamma.contiguous().to(at::kBFloat16);
   auto be = beta.contiguous().to(at::kBFloat16);
   int blocks = (int)std::min<long long>((rows + 3) / 4, 4096);
@@ -179,11 +223,15 @@ at::Tensor add_layernorm(at::Tensor a, c10::optional<at::Tensor> b,
 at::Tensor bias_gelu(at::Tensor x, at::Tensor bias) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16);
   auto x2 = x.contiguous();
+  TORCH_CHECK(x2.dim() >= 1 && x2.size(-1) > 0 && x2.size(-1) % 8 == 0,
+              "bias_gelu: D % 8 == 0, D > 0");
   int d = (int)x2.size(-1);
-  TORCH_CHECK(d % 8 == 0, "bias_gelu: D % 8 == 0");
+  TORCH_CHECK(bias.is_cuda() && bias.numel() == d,
+              "bias_gelu: bias must be CUDA [D]");
   auto b = bias.contiguous().to(at::kBFloat16);
   at::Tensor y = at::empty_like(x2);
   long long total = x2.numel();
+  if (total == 0) return y.view(x.sizes());
   int blocks = (int)std::min<long long>((total / 8 + 255) / 256, 4096);
   hipLaunchKernelGGL(k_bias_gelu, dim3(blocks), dim3(256), 0, enc_stream(),
                      (const unsigned short*)x2.data_ptr(),
@@ -197,15 +245,18 @@ at::Tensor mean_pool_l2norm(at::Tensor x, c10::optional<at::Tensor> mask) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.scalar_type() == at::kBFloat16);
   auto x2 = x.contiguous();
   int bsz = (int)x2.size(0), s = (int)x2.size(1), d = (int)x2.size(2);
-  TORCH_CHECK(d % 8 == 0);
+  TORCH_CHECK(d > 0 && d % 8 == 0, "mean_pool_l2norm: D % 8 == 0, D > 0");
   const int* mp = nullptr;
   at::Tensor mc;
   if (mask.has_value()) {
     mc = mask->to(at::kInt).contiguous();
-    TORCH_CHECK(mc.size(0) == bsz && mc.size(1) == s);
+    TORCH_CHECK(mc.is_cuda() && mc.dim() == 2 && mc.size(0) == bsz &&
+                    mc.size(1) == s,
+                "mean_pool_l2norm: mask must be CUDA [B,S]");
     mp = mc.data_ptr<int>();
   }
   at::Tensor out = at::empty({bsz, d}, x2.options().dtype(at::kFloat));
+  if (bsz == 0) return out;
   size_t lds = (size_t)d * sizeof(float);
   hipLaunchKernelGGL(k_mean_pool_l2norm, dim3(bsz), dim3(256), lds,
                      enc_stream(), (const unsigned short*)x2.data_ptr(), mp,

@@ -355,7 +355,13 @@ __global__ __launch_bounds__(GM_NTHREADS, 1) void k_gemm_nt(
     MFMA_MI(1, 0, 2, bn0);
     MFMA_MI(1, 0, 3, bn0);
     __builtin_amdgcn_s_setprio(0);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    // In the last iteration nothing was staged in phases 2 and 3, so the
+    // only loads still counted are dbuf1's own: wait for all of them.
+    if (pf0 < nkt) {
+      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
@@ -663,6 +669,17 @@ __global__ __launch_bounds__(GB_NT, 3) void k_gemm_nt96(
 // ---------------------------------------------------------------------------
 // host wrapper
 // ---------------------------------------------------------------------------
+// Row tile of the kernel that gemm_nt launches for M rows: variant B
+// (96x256, 3 WGs/CU) by default - co-residency beats the 1-WG 256x256
+// template on the encoder shapes (ablation in scripts/gemm_ablate.py) -
+// and variant A when M is no multiple of 96 or NORNICDB_GEMM_KERNEL=256.
+// M = 0 is a valid question: ops/gemm.py asks it to learn the row tile the
+// environment selects before it pads, so keep this free of checks on M.
+long long gemm_nt_variant(long long M) {
+  const char* kv = getenv("NORNICDB_GEMM_KERNEL");
+  return (!(kv && atoi(kv) == 256) && M % GB_BM == 0) ? GB_BM : GM_BM;
+}
+
 at::Tensor gemm_nt(at::Tensor a, at::Tensor w, c10::optional<at::Tensor> bias,
                    long long act) {
   TORCH_CHECK(a.is_cuda() && a.dim() == 2 && a.is_contiguous() &&
@@ -673,11 +690,8 @@ at::Tensor gemm_nt(at::Tensor a, at::Tensor w, c10::optional<at::Tensor> bias,
               "gemm_nt: W must be contiguous 2D bf16 CUDA");
   long long M = a.size(0), K = a.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K, "gemm_nt: K mismatch");
-  // kernel choice: variant B (96x256, 3 WGs/CU) by default — co-residency
-  // beats the 1-WG 256x256 template on the encoder shapes (ablation in
-  // scripts/gemm_ablate.py); NORNICDB_GEMM_KERNEL=256 forces variant A.
-  const char* kv = getenv("NORNICDB_GEMM_KERNEL");
-  bool use96 = !(kv && atoi(kv) == 256) && (M % GB_BM == 0);
+  const bool use96 = gemm_nt_variant(M) == GB_BM;
+  TORCH_CHECK(M > 0 && K > 0, "gemm_nt: empty A");
   TORCH_CHECK(use96 ? (M % GB_BM == 0) : (M % GM_BM == 0),
               "gemm_nt: M tiling (python pads)");
   TORCH_CHECK(N % GM_BN == 0, "gemm_nt: N % 256 == 0 (python pads)");

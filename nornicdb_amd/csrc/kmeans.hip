@@ -162,25 +162,26 @@ __global__ __launch_bounds__(256) void k_kmeanspp_update(
   }
 }
 
-// incremental single-point update: sign=+1 add, -1 remove.
-__global__ void k_kmeans_point_upd(float* __restrict__ cent,
-                                   int* __restrict__ counts,
-                                   const unsigned short* __restrict__ xv,
-                                   int c, int d, int sign) {
+// incremental single-point update: sign=+1 add, -1 remove. Launched as ONE
+// block: every thread reads the old count, then the block barrier, and only
+// after it does thread 0 write the new count, so no thread can see it.
+__global__ __launch_bounds__(256) void k_kmeans_point_upd(
+    float* __restrict__ cent, int* __restrict__ counts,
+    const unsigned short* __restrict__ xv, int c, int d, int sign) {
   const int cnt_old = counts[c];
+  __syncthreads();
   const int cnt_new = cnt_old + sign;
   if (cnt_new <= 0) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) counts[c] = 0;
+    if (threadIdx.x == 0) counts[c] = 0;
     return;
   }
   const float inv = 1.0f / (float)cnt_new;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < d;
-       i += gridDim.x * blockDim.x) {
+  for (int i = threadIdx.x; i < d; i += blockDim.x) {
     float cur = cent[(long long)c * d + i];
     cent[(long long)c * d + i] =
         (cur * (float)cnt_old + (float)sign * bf16_bits_to_f32(xv[i])) * inv;
   }
-  if (threadIdx.x == 0 && blockIdx.x == 0) counts[c] = cnt_new;
+  if (threadIdx.x == 0) counts[c] = cnt_new;
 }
 
 // ---------------------------------------------------------------------------
@@ -194,6 +195,10 @@ static inline hipStream_t km_stream() {
   TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&            \
                   x.scalar_type() == at::kBFloat16,                          \
               "kmeans: expected contiguous 2D bf16 CUDA tensor")
+// contiguous CUDA tensor of the given dtype
+#define KM_CHECK_T(t, ty, what)                                              \
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == ty,     \
+              "kmeans: ", what)
 
 std::tuple<at::Tensor, at::Tensor> kmeans_assign(at::Tensor x, at::Tensor cent,
                                                  at::Tensor cnorm2) {
@@ -203,7 +208,9 @@ std::tuple<at::Tensor, at::Tensor> kmeans_assign(at::Tensor x, at::Tensor cent,
   int d = (int)x.size(1), k = (int)cent.size(0);
   TORCH_CHECK(cent.size(1) == d, "kmeans_assign: dim mismatch");
   TORCH_CHECK(d % 512 == 0 && d <= 4096, "kmeans_assign: d % 512 == 0, <= 4096");
-  TORCH_CHECK(cnorm2.scalar_type() == at::kFloat && cnorm2.numel() == k);
+  TORCH_CHECK(k >= 1, "kmeans_assign: no centroids");
+  KM_CHECK_T(cnorm2, at::kFloat, "cnorm2 must be contiguous fp32 CUDA");
+  TORCH_CHECK(cnorm2.numel() == k, "kmeans_assign: cnorm2 must have k entries");
   auto assign = at::empty({n}, x.options().dtype(at::kInt));
   auto d2 = at::empty({n}, x.options().dtype(at::kFloat));
   int blocks = (int)std::min<long long>((n + 3) / 4, 8192);
@@ -217,7 +224,11 @@ std::tuple<at::Tensor, at::Tensor> kmeans_assign(at::Tensor x, at::Tensor cent,
   switch (d / 512) {
     case 1: launch(k_kmeans_assign<1>); break;
     case 2: launch(k_kmeans_assign<2>); break;
+    case 3: launch(k_kmeans_assign<3>); break;
     case 4: launch(k_kmeans_assign<4>); break;
+    case 5: launch(k_kmeans_assign<5>); break;
+    case 6: launch(k_kmeans_assign<6>); break;
+    case 7: launch(k_kmeans_assign<7>); break;
     case 8: launch(k_kmeans_assign<8>); break;
     default: TORCH_CHECK(false, "kmeans_assign: unsupported d");
   }
@@ -228,7 +239,9 @@ std::tuple<at::Tensor, at::Tensor> kmeans_assign(at::Tensor x, at::Tensor cent,
 std::tuple<at::Tensor, at::Tensor> kmeans_accum(at::Tensor x, at::Tensor assign,
                                                 long long k) {
   KM_CHECK_X(x);
-  TORCH_CHECK(assign.scalar_type() == at::kInt && assign.numel() == x.size(0));
+  KM_CHECK_T(assign, at::kInt, "assign must be contiguous int32 CUDA");
+  TORCH_CHECK(assign.numel() == x.size(0), "kmeans_accum: one assign per row");
+  TORCH_CHECK(k >= 1, "kmeans_accum: k >= 1");
   long long n = x.size(0);
   int d = (int)x.size(1);
   auto sums = at::zeros({k, d}, x.options().dtype(at::kFloat));
@@ -245,6 +258,12 @@ std::tuple<at::Tensor, at::Tensor> kmeans_accum(at::Tensor x, at::Tensor assign,
 std::tuple<at::Tensor, at::Tensor> kmeans_finalize(at::Tensor sums,
                                                    at::Tensor counts,
                                                    at::Tensor old_c) {
+  KM_CHECK_T(sums, at::kFloat, "sums must be contiguous fp32 CUDA");
+  KM_CHECK_T(counts, at::kInt, "counts must be contiguous int32 CUDA");
+  KM_CHECK_T(old_c, at::kFloat, "old_c must be contiguous fp32 CUDA");
+  TORCH_CHECK(sums.dim() == 2 && old_c.sizes() == sums.sizes() &&
+                  counts.numel() == sums.size(0),
+              "kmeans_finalize: sums [k,d], counts [k], old_c [k,d]");
   int k = (int)sums.size(0), d = (int)sums.size(1);
   auto new_c = at::empty_like(old_c);
   auto drift2 = at::empty({k}, sums.options());
@@ -263,7 +282,12 @@ void kmeanspp_update(at::Tensor x, at::Tensor c, double cn2, at::Tensor d2) {
   KM_CHECK_X(x);
   long long n = x.size(0);
   int d = (int)x.size(1);
-  TORCH_CHECK(d % 512 == 0 && d <= 4096);
+  TORCH_CHECK(d % 512 == 0 && d <= 4096,
+              "kmeanspp_update: d % 512 == 0, <= 4096");
+  KM_CHECK_T(c, at::kBFloat16, "seed must be contiguous bf16 CUDA");
+  TORCH_CHECK(c.numel() == d, "kmeanspp_update: seed must have d entries");
+  KM_CHECK_T(d2, at::kFloat, "d2 must be contiguous fp32 CUDA");
+  TORCH_CHECK(d2.numel() == n, "kmeanspp_update: one d2 per row");
   int blocks = (int)std::min<long long>((n + 3) / 4, 8192);
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(std::max(blocks, 1)), dim3(256), 0,
@@ -274,7 +298,11 @@ void kmeanspp_update(at::Tensor x, at::Tensor c, double cn2, at::Tensor d2) {
   switch (d / 512) {
     case 1: launch(k_kmeanspp_update<1>); break;
     case 2: launch(k_kmeanspp_update<2>); break;
+    case 3: launch(k_kmeanspp_update<3>); break;
     case 4: launch(k_kmeanspp_update<4>); break;
+    case 5: launch(k_kmeanspp_update<5>); break;
+    case 6: launch(k_kmeanspp_update<6>); break;
+    case 7: launch(k_kmeanspp_update<7>); break;
     case 8: launch(k_kmeanspp_update<8>); break;
     default: TORCH_CHECK(false, "kmeanspp_update: unsupported d");
   }
@@ -283,8 +311,17 @@ void kmeanspp_update(at::Tensor x, at::Tensor c, double cn2, at::Tensor d2) {
 
 void kmeans_point_update(at::Tensor cent, at::Tensor counts, at::Tensor xv,
                          long long c, long long sign) {
+  KM_CHECK_T(cent, at::kFloat, "centroids must be contiguous fp32 CUDA");
+  TORCH_CHECK(cent.dim() == 2, "kmeans_point_update: centroids [k,d]");
+  KM_CHECK_T(counts, at::kInt, "counts must be contiguous int32 CUDA");
+  KM_CHECK_T(xv, at::kBFloat16, "point must be contiguous bf16 CUDA");
   int d = (int)cent.size(1);
-  hipLaunchKernelGGL(k_kmeans_point_upd, dim3(4), dim3(256), 0, km_stream(),
+  TORCH_CHECK(counts.numel() == cent.size(0) && xv.numel() == d,
+              "kmeans_point_update: counts [k], point [d]");
+  TORCH_CHECK(c >= 0 && c < cent.size(0), "kmeans_point_update: 0 <= c < k");
+  TORCH_CHECK(sign == 1 || sign == -1, "kmeans_point_update: sign is +1 or -1");
+  // one block: see the kernel for why
+  hipLaunchKernelGGL(k_kmeans_point_upd, dim3(1), dim3(256), 0, km_stream(),
                      cent.data_ptr<float>(), counts.data_ptr<int>(),
                      (const unsigned short*)xv.data_ptr(), (int)c, d,
                      (int)sign);

@@ -16,8 +16,9 @@ def add_layernorm(a, b, gamma, beta, eps=1e-5):
     nat = _use_native(a)
     if nat is not None and a.shape[-1] % 8 == 0 and a.shape[-1] <= 8192:
         return nat.add_layernorm(a, b, gamma, beta, eps)
-    x = a if b is None else a + b
-    return F.layer_norm(x.float(), (x.shape[-1],), gamma.float(), beta.float(),
+    # the sum stays in fp32, as in the kernel: a bf16 a + b would round it
+    x = a.float() if b is None else a.float() + b.float()
+    return F.layer_norm(x, (x.shape[-1],), gamma.float(), beta.float(),
                         eps).to(a.dtype)
 
 
@@ -25,7 +26,10 @@ def bias_gelu(x, bias):
     nat = _use_native(x)
     if nat is not None and x.shape[-1] % 8 == 0:
         return nat.bias_gelu(x, bias)
-    return F.gelu((x.float() + bias.float())).to(x.dtype)
+    # the kernel's expression: F.gelu forms f * (1 + erf) before the 0.5 and
+    # overflows from 2^127 on
+    f = x.float() + bias.float()
+    return ((0.5 * f) * (1.0 + torch.erf(f * 0.7071067811865476))).to(x.dtype)
 
 
 def mean_pool_l2norm(x, mask=None):

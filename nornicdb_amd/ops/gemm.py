@@ -1,12 +1,20 @@
 """Hand-written MFMA GEMM dispatch for the encoder hot path.
 
 `linear_act(x, weight, bias, act)` computes act(x @ weight.T + bias) with
-the 256x256 8-phase CDNA4 MFMA kernel (csrc/gemm.hip) when the operands
-are bf16 CUDA and the shapes tile cleanly; otherwise it falls back to the
-plain PyTorch expression (which is also the CPU numerics oracle).
+a hand-written CDNA4 MFMA kernel (csrc/gemm.hip) when NORNICDB_GEMM=hand,
+the operands are bf16 CUDA and the shapes tile cleanly (N % 256 == 0,
+K % 128 == 0); otherwise, and by default ("auto"), it uses the plain
+PyTorch expression (the library GEMM on the GPU, with the hand-written
+bias_gelu kernel behind it for GELU; also the CPU numerics oracle).
 
-This retires hipBLASLt (Tensile Cijk_* kernels) from the bge-m3 forward
-pass; the replaced reference units are the cublas scoring GEMV
+Two kernels: variant B (96x256 tile, 3 workgroups per CU) runs whenever M
+is a multiple of 96, and gemm_nt pads M to make it so; variant A (256x256,
+8-phase, one workgroup per CU) runs only under NORNICDB_GEMM_KERNEL=256 or
+for a direct native call with M % 96 != 0. `_C.gemm_nt_variant(M)` tells
+which one a call launches. tests/test_gemm_kernels.py runs both.
+
+With NORNICDB_GEMM=hand this retires hipBLASLt (Tensile Cijk_* kernels)
+from the bge-m3 forward pass; the replaced reference units are the cublas scoring GEMV
 (pkg/gpu/cuda/cuda_kernels.cu:340-375) and llama.cpp's encoder GEMMs
 (pkg/localllm/llama.go).
 
@@ -34,8 +42,9 @@ ACT_GELU = 1
 # hipBLASLt's 791-1478 TF, and hardware ablation shows the residual gap
 # is Tensile's deep-pipelined hand-asm K-loop, not occupancy or LDS
 # conflicts. "auto" routes to the faster library per VERDICT r1 item 2's
-# explicit fallback rule; the hand kernels are one env var away and
-# numerics-tested.
+# explicit fallback rule; the hand kernels are one env var away. Both are
+# numerics-tested in tests/test_gemm_kernels.py, which asserts the variant
+# that ran.
 _MODE = os.environ.get("NORNICDB_GEMM", "auto").lower()
 _FORCE_LIB = _MODE in ("blaslt", "lib", "0", "auto")
 _FORCE_HAND = _MODE in ("hand", "mfma", "1")
@@ -51,7 +60,10 @@ def gemm_nt(x2d, weight, bias=None, act=ACT_NONE):
     256 for NORNICDB_GEMM_KERNEL=256 variant A)."""
     nat = native_or_none()
     m = x2d.shape[0]
-    tile = 256 if os.environ.get("NORNICDB_GEMM_KERNEL") == "256" else 96
+    # the row tile the environment selects: every tile divides M = 0, so
+    # the answer for 0 depends on NORNICDB_GEMM_KERNEL alone (gemm_nt_variant
+    # in csrc/gemm.hip keeps M = 0 valid for this)
+    tile = nat.gemm_nt_variant(0)
     mp = (m + tile - 1) // tile * tile
     if mp != m:
         xpad = x2d.new_zeros((mp, x2d.shape[1]))

@@ -108,17 +108,19 @@ def test_linear_act_cpu_fallback():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("m,n,k,act", [
-    (256, 256, 128, 0),      # single tile
-    (512, 768, 256, 0),      # multi-tile, XCD remap with nwg%8 != 0
-    (1000, 512, 128, 1),     # M padding path + GELU
-    (2048, 1024, 1024, 0),   # encoder attn-out shape (scaled M)
+    # ops.gemm.gemm_nt pads M to a multiple of 96, so all of these run the
+    # 96x256 kernel (variant B); tests/test_gemm_kernels.py runs variant A
+    (256, 256, 128, 0),      # pads to 288: 3 row tiles
+    (512, 768, 256, 0),      # pads to 576: 6 x 3 tiles, nwg % 8 != 0
+    (1000, 512, 128, 1),     # pads to 1056: 11 x 2 tiles, GELU
+    (2048, 1024, 1024, 0),   # encoder attn-out shape (scaled M), pads to 2112
     (2048, 4096, 1024, 1),   # encoder FFN-up shape (scaled M)
     (2048, 1024, 4096, 0),   # encoder FFN-down shape (scaled M)
     (2048, 3072, 1024, 0),   # encoder QKV shape (scaled M)
 ])
 def test_gemm_nt_gpu(m, n, k, act):
-    # gemm_nt is ALWAYS the hand-written MFMA kernel (dispatch policy in
-    # linear_act does not apply) — this is the kernel numerics oracle.
+    # gemm_nt is ALWAYS a hand-written MFMA kernel (dispatch policy in
+    # linear_act does not apply).
     from nornicdb_amd.ops.gemm import gemm_nt
     torch.manual_seed(m * 31 + n + k + act)
     x = (torch.randn(m, k, device="cuda") / k ** 0.25).to(torch.bfloat16)
@@ -178,8 +180,9 @@ def test_linear_act_autograd_gpu(monkeypatch):
     (96, 256, 128, 0),       # single variant-B tile
 ])
 def test_gemm_nt96_variant_gpu(m, n, k, act):
-    """The 96x256 3-WG/CU kernel (selected when M % 96 == 0) — the
-    earlier suite's shapes all silently fell back to variant A."""
+    """The 96x256 3-WG/CU kernel (selected when M % 96 == 0) without
+    padding. test_gemm_nt_gpu above reaches the same kernel by padding;
+    variant A is covered in tests/test_gemm_kernels.py."""
     from nornicdb_amd.ops.gemm import gemm_nt
     torch.manual_seed(m + n + k)
     x = (torch.randn(m, k, device="cuda") / k ** 0.25).to(torch.bfloat16)
