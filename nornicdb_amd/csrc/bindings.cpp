@@ -83,6 +83,16 @@ at::Tensor labelprop_step(at::Tensor row_ptr, at::Tensor col_idx,
 void wcc_hook(at::Tensor row_ptr, at::Tensor col_idx, at::Tensor comp,
               at::Tensor changed, long long row_base);
 
+// centrality.hip
+void msbfs_level(at::Tensor in_row_ptr, at::Tensor in_col_idx,
+                 at::Tensor frontier, at::Tensor visited, at::Tensor next,
+                 at::Tensor level_count, long long full_mask);
+void bc_forward(at::Tensor in_row_ptr, at::Tensor in_col_idx, at::Tensor dist,
+                at::Tensor sigma, at::Tensor changed, long long level);
+void bc_backward(at::Tensor row_ptr, at::Tensor col_idx, at::Tensor dist,
+                 at::Tensor sigma, at::Tensor delta, long long level);
+void bc_accumulate(at::Tensor delta, at::Tensor sources, at::Tensor bc);
+
 // packstream.cpp (CPU)
 pybind11::bytes ps_pack(pybind11::object v);
 pybind11::object ps_unpack(pybind11::buffer data,
@@ -246,6 +256,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bfs_level", &bfs_level, "BFS frontier level expansion");
   m.def("labelprop_step", &labelprop_step, "label propagation step");
   m.def("wcc_hook", &wcc_hook, "connected-components hook step");
+  m.def("msbfs_level", &msbfs_level,
+        "multi-source BFS level over the in-edge CSR, 64 sources per uint64 "
+        "word (held as int64): next = OR frontier[in-nbrs] & ~visited, "
+        "visited |= next, level_count[64] += newly reached per source bit");
+  m.def("bc_forward", &bc_forward,
+        "Brandes forward level over the in-edge CSR for dist/sigma [B][n]");
+  m.def("bc_backward", &bc_backward,
+        "Brandes backward level over the out-edge CSR for delta [B][n]");
+  m.def("bc_accumulate", &bc_accumulate,
+        "bc[v] += delta[b][v] for b in order, skipping v == sources[b]");
   m.def("ps_pack", &ps_pack, "PackStream encode (native)");
   m.def("ps_unpack", &ps_unpack, "PackStream decode (native)",
         py::arg("data"), py::arg("structure_factory"));

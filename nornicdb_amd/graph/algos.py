@@ -10,6 +10,7 @@ Triangles, ClusteringCoeff, ConnectedComponents).
 from __future__ import annotations
 
 import heapq
+import os
 from collections import defaultdict
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -23,8 +24,9 @@ GPU_MIN_EDGES = 50_000  # below this the numpy path wins on latency
 
 
 def _use_gpu(g: CSRGraph, device=None) -> bool:
-    return (torch.cuda.is_available() and native_or_none() is not None
-            and g.m >= GPU_MIN_EDGES and device != "cpu")
+    # the cheap tests first: a small graph never touches the extension
+    return (device != "cpu" and g.m >= GPU_MIN_EDGES
+            and torch.cuda.is_available() and native_or_none() is not None)
 
 
 # ---------------------------------------------------------------- PageRank
@@ -269,8 +271,11 @@ def degree_centrality(g: CSRGraph) -> np.ndarray:
     return (deg / denom).astype(np.float32)
 
 
-def closeness_centrality(g: CSRGraph, nodes: Sequence[int] = None) -> np.ndarray:
+def closeness_centrality(g: CSRGraph, nodes: Sequence[int] = None,
+                         device=None) -> np.ndarray:
     nodes = range(g.n) if nodes is None else nodes
+    if _use_gpu(g, device):
+        return _closeness_gpu(g, nodes)
     out = np.zeros(g.n, np.float32)
     for u in nodes:
         d = bfs_distances(g, u, device="cpu")
@@ -280,16 +285,135 @@ def closeness_centrality(g: CSRGraph, nodes: Sequence[int] = None) -> np.ndarray
     return out
 
 
-def betweenness_centrality(g: CSRGraph, samples: int = None,
-                           seed: int = 0) -> np.ndarray:
-    """Brandes' algorithm (exact, or source-sampled approximation)."""
+def _closeness_gpu(g: CSRGraph, nodes: Sequence[int]) -> np.ndarray:
+    """Multi-source BFS, 64 sources per uint64 word (held as int64): per
+    level one `msbfs_level` launch over the in-edge CSR and one readback of
+    the 64 per-source counts of newly reached vertices. The integer counts
+    feed the same float64 quotient as the CPU path, so the result is
+    bit-identical to it."""
+    nat = native_or_none()
+    dev = "cuda"
     n = g.n
-    bc = np.zeros(n)
+    out = np.zeros(n, np.float32)
+    nodes = np.asarray(list(nodes), dtype=np.int64)
+    if n == 0 or nodes.size == 0:
+        return out
+    if nodes.min() < 0 or nodes.max() >= n:
+        raise IndexError("closeness_centrality: node index out of range")
+    rp, ci = g.torch_csr(dev, in_edges=True)
+    frontier = torch.empty(n, dtype=torch.int64, device=dev)
+    visited = torch.empty(n, dtype=torch.int64, device=dev)
+    nxt = torch.empty(n, dtype=torch.int64, device=dev)
+    level_count = torch.zeros(64, dtype=torch.int64, device=dev)
+    for b0 in range(0, nodes.size, 64):
+        batch = nodes[b0:b0 + 64]
+        nb = batch.size
+        # a node listed twice in one batch owns two bits of one word
+        uniq, inv = np.unique(batch, return_inverse=True)
+        words = np.zeros(uniq.size, np.uint64)
+        np.bitwise_or.at(words, inv,
+                         np.uint64(1) << np.arange(nb, dtype=np.uint64))
+        # exactly the bits of the batch's real sources, as an int64 pattern
+        full = int(np.bitwise_or.reduce(words, keepdims=True).view(np.int64)[0])
+        idx = torch.as_tensor(uniq, device=dev)
+        wt = torch.as_tensor(words.view(np.int64), device=dev)
+        frontier.zero_()
+        frontier[idx] = wt
+        visited.copy_(frontier)
+        sum_dist = np.zeros(64, np.int64)
+        reach = np.ones(64, np.int64)
+        level = 0
+        while True:
+            level_count.zero_()
+            nat.msbfs_level(rp, ci, frontier, visited, nxt, level_count, full)
+            cnt = level_count.cpu().numpy()
+            if not cnt.any():
+                break
+            sum_dist += (level + 1) * cnt
+            reach += cnt
+            frontier, nxt = nxt, frontier
+            level += 1
+        for b in range(nb):
+            if reach[b] > 1:
+                out[batch[b]] = (int(reach[b]) - 1) / sum_dist[b]
+    return out
+
+
+def _bc_sources(n: int, samples: Optional[int], seed: int):
+    """The sources and the scale of betweenness_centrality, shared by the
+    CPU and the device route."""
     rng = np.random.default_rng(seed)
     sources = list(rng.choice(n, min(samples, n), replace=False)) \
         if samples else list(range(n))
-    rp, ci = g.row_ptr, g.col_idx
     scale = (n / max(len(sources), 1)) if samples else 1.0
+    return sources, scale
+
+
+BC_BATCH_BUDGET = 1 << 30  # bytes of dist + sigma + delta state per batch
+
+
+def _bc_batch(n_sources: int, n: int) -> int:
+    """Sources per launch: at most 32, and dist (4) + sigma (8) + delta (8)
+    = 20 bytes per source and vertex within the budget (1 GiB, or
+    NORNICDB_BC_BATCH bytes)."""
+    budget = int(os.environ.get("NORNICDB_BC_BATCH") or BC_BATCH_BUDGET)
+    return max(1, min(n_sources, 32, budget // (20 * max(n, 1))))
+
+
+def _betweenness_gpu(g: CSRGraph, sources: Sequence[int],
+                     scale: float) -> np.ndarray:
+    """Brandes' algorithm on the device, a batch of sources per launch:
+    `bc_forward` levels over the in-edge CSR until nothing changes, then
+    `bc_backward` from the deepest level down to 0 over the out-edge CSR and
+    `bc_accumulate` into the float64 sum. No atomics; the result does not
+    depend on the batch size."""
+    nat = native_or_none()
+    dev = "cuda"
+    n = g.n
+    sources = np.asarray(list(sources), dtype=np.int64)
+    if n == 0 or sources.size == 0:
+        return np.zeros(n, np.float32)
+    rp, ci = g.torch_csr(dev)
+    irp, ici = g.torch_csr(dev, in_edges=True)
+    nbatch = _bc_batch(sources.size, n)
+    dist = torch.empty(nbatch, n, dtype=torch.int32, device=dev)
+    sigma = torch.empty(nbatch, n, dtype=torch.float64, device=dev)
+    delta = torch.empty(nbatch, n, dtype=torch.float64, device=dev)
+    bc = torch.zeros(n, dtype=torch.float64, device=dev)
+    changed = torch.zeros(1, dtype=torch.int32, device=dev)
+    for b0 in range(0, sources.size, nbatch):
+        src = torch.as_tensor(sources[b0:b0 + nbatch], device=dev)
+        nb = src.numel()
+        d, s, dl = dist[:nb], sigma[:nb], delta[:nb]
+        rows = torch.arange(nb, device=dev)
+        d.fill_(-1)
+        s.zero_()
+        dl.zero_()
+        d[rows, src] = 0
+        s[rows, src] = 1.0
+        level = 0
+        while True:
+            changed.zero_()
+            nat.bc_forward(irp, ici, d, s, changed, level)
+            if int(changed.item()) == 0:
+                break
+            level += 1
+        # `level` is the deepest level any source of the batch reached
+        for lv in range(level - 1, -1, -1):
+            nat.bc_backward(rp, ci, d, s, dl, lv)
+        nat.bc_accumulate(dl, src, bc)
+    return (bc.cpu().numpy() * scale).astype(np.float32)
+
+
+def betweenness_centrality(g: CSRGraph, samples: int = None,
+                           seed: int = 0, device=None) -> np.ndarray:
+    """Brandes' algorithm (exact, or source-sampled approximation)."""
+    n = g.n
+    sources, scale = _bc_sources(n, samples, seed)
+    if _use_gpu(g, device):
+        return _betweenness_gpu(g, sources, scale)
+    bc = np.zeros(n)
+    rp, ci = g.row_ptr, g.col_idx
     for s in sources:
         stack = []
         preds = [[] for _ in range(n)]
